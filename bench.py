@@ -7,9 +7,17 @@ fused Adam) on synthetic 8x3x400x600 fp32 batches per GPU -- BASELINE.json confi
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  `value` = images/s over all ranks (weak scaling: 8 images per rank).
+A plain run sets up, warms up, times --steps steps and prints the line; everything else is behind --full:
 `roofline` is measured live with HIP events (torch.cuda.Event on the launch stream) around every
 launch of the dominant kernel family in extra, separately-run steps; `cpu_baseline` times the CPU
-oracle (oracle/cidnet_oracle.py, a port of the reference's algorithm) on a bounded sample.
+oracle (oracle/cidnet_oracle.py, a port of the reference's algorithm) on a bounded sample;
+`bf16_mode`, `inference_1024` and `variants_bs16` are the other BASELINE.json configs.  Without --full
+these keys are null.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0): DIR/loss.npy, DIR/grads.npy (the
+flat gradient of the live parameters) and DIR/params.npy (the flat parameters after its Adam update), all
+float32.  The weights and the optimizer state are reset to their seeded initial values after the set-up
+steps, so with the same arguments these depend on nothing but the build.
 """
 import argparse
 import json
@@ -38,12 +46,16 @@ def parse():
     ap.add_argument("--width", type=int, default=600)
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="storage type of the IEL chain's hidden tensors (arithmetic is fp32 either way); f32 is the parity mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the rooflines (2 extra instrumented steps), the bf16-mode step, 1024x1024 inference, "
+                         "the MSSA / TNSM variants and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, gradients and updated parameters as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-inference-leg", action="store_true",
-                    help="skip the legs after the timed region: the bf16-mode step (configs[2]), 32x3x1024x1024 inference (configs[3]), the variants (configs[4])")
+                    help="with --full: skip the legs after the timed region: the bf16-mode step (configs[2]), 32x3x1024x1024 inference (configs[3]), the variants (configs[4])")
     ap.add_argument("--no-prepared-weights", action="store_true", help="A/B: prepare the bf16x3 weight operands per launch (as a plain model(x) call does)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the MSSA / TNSM bs=16 measurement (configs[4])")
-    ap.add_argument("--op-table", action="store_true", help="print per-entry-point time shares to stderr")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the MSSA / TNSM bs=16 measurement (configs[4])")
+    ap.add_argument("--op-table", action="store_true", help="print per-entry-point time shares to stderr (runs the instrumented steps)")
     ap.add_argument("--op-rows", type=int, default=70, help="rows of the per-shape part of --op-table")
     ap.add_argument("--no-wgrad-stream", action="store_true", help="keep the weight-gradient GEMMs on the branch streams")
     ap.add_argument("--graph", action="store_true", help="replay forward+backward as one hipGraph (experiment)")
@@ -315,6 +327,29 @@ def settle(trainer, x, gt, dev, world=1, max_steps=12):
     torch.cuda.synchronize()
 
 
+def restart(trainer, init):
+    """Weights back to their seeded initial values `init` (model.parameters() order) and a fresh Adam state: settle() runs
+    as many steps as the allocator needs, and the steps after it must compute the same thing from run to run."""
+    with torch.no_grad():
+        for p, p0 in zip(trainer.model.parameters(), init):
+            p.copy_(p0)
+    trainer.opt.m.zero_()
+    trainer.opt.v.zero_()
+    trainer.opt.t = 0
+    trainer.weights_changed()
+    if trainer.flat_p.is_cuda:
+        torch.cuda.synchronize()
+
+
+def dump_outputs(out_dir, trainer, loss):
+    """What the last timed step hands its caller: the loss, the gradient it reduced and the parameters Adam wrote."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1), "grads": trainer.flat_g[:trainer.n_live], "params": trainer.flat_p}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def bf16_mode_leg(a, dev, world, local, rank, f32_ms):
     """configs[2]'s numeric mode on the SAME box right after the fp32 timed region: P.set_precision("bf16") -- convolution
     operands rounded to bf16 on the matrix cores (one product per term, fp32 accumulation) and the LCA-internal tensors
@@ -444,7 +479,10 @@ def main():
             dist.barrier(device_ids=[local])
             torch.cuda.synchronize()
 
+    init = [p.detach().cpu() for p in model.parameters()]      # host copy: the set-up steps size the allocator as before
     settle(trainer, x, gt, dev, world)                  # set-up steps (allocator footprint), see settle()
+    restart(trainer, init)
+    del init
     sync()
     for _ in range(max(a.warmup, 1)):
         loss = trainer.step(x, gt)
@@ -480,6 +518,8 @@ def main():
         dt = t.item()
     lossv = float(loss.item())
     assert lossv == lossv, "loss is NaN"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, trainer, loss)
 
     # ---- roofline of the dominant kernel family (dense 3x3 conv on the fp32 MFMA), live events ----
     # every rank runs these extra steps (they contain the gradient all-reduce); only rank 0 instruments
@@ -487,17 +527,20 @@ def main():
     # streams of the timed region, launches of different families overlap and an event pair would charge a
     # kernel for the time it shares the GPU with the other branch.
     from hvi_cidnet_amd import ops as _ops
-    model.two_streams = False
-    _ops.enable_wgrad_stream(False)
-    graph_mode, trainer.use_graph = trainer.use_graph, False      # the instrumented steps launch eagerly
-    timer = OpTimer().install() if rank == 0 else None
-    for _ in range(2):
-        trainer.step(x, gt)
-    sync()
-    model.two_streams = not a.single_stream
-    trainer.use_graph = graph_mode
-    _ops.enable_wgrad_stream(trainer.wgrad_stream)
-    if rank == 0:
+    instrument = a.full or a.op_table
+    roof = roof_pw = roof_hbm = None
+    if instrument:
+        model.two_streams = False
+        _ops.enable_wgrad_stream(False)
+        graph_mode, trainer.use_graph = trainer.use_graph, False      # the instrumented steps launch eagerly
+        timer = OpTimer().install() if rank == 0 else None
+        for _ in range(2):
+            trainer.step(x, gt)
+        sync()
+        model.two_streams = not a.single_stream
+        trainer.use_graph = graph_mode
+        _ops.enable_wgrad_stream(trainer.wgrad_stream)
+    if rank == 0 and instrument:
         agg = timer.table()
         timer.remove()
         tot = sum(v[1] for v in agg.values())
@@ -570,7 +613,7 @@ def main():
     # the 1024x1024 inference leg runs on EVERY rank (north_star: both sizes at 1/2/4/8 GPUs); the variants on rank 0 at N = 1
     infer = variants = bf16 = None
     default_cfg = (a.height, a.width, a.batch) == (400, 600, 8)
-    if not a.no_inference_leg and default_cfg:
+    if a.full and not a.no_inference_leg and default_cfg:
         del trainer
         _ops.set_grad_arena(None, None)
         _ops.clear_prepared_weights()
@@ -582,7 +625,7 @@ def main():
             variants = variants_bs16(dev)
     if rank == 0:
         cpu = None
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cpu = cpu_baseline(a)
 
         out = {
@@ -593,7 +636,7 @@ def main():
             "vs_baseline": None, "dtype": "f32" if a.dtype == "f32" else "bf16 (matrix-core operands rounded to bf16, fp32 accumulation; bf16 storage of the LCA-internal tensors)", "data": "synthetic",
             "config": {"workload": f"CIDNet fwd+bwd bs={a.batch}/GPU 3x{a.height}x{a.width} fp32 (BASELINE.json configs[1])",
                        "global_batch": world * a.batch, "parallelism": f"dp{world}", "rccl_ranks": (dist.get_world_size() if dist.is_initialized() else 1), "streams": 1 if a.single_stream else (2 if a.no_wgrad_stream else 3), "loss": round(lossv, 6)},
-            "roofline": roof if a.dtype == "f32" else dict(roof_hbm, mfma_conv3=roof), "roofline_pw": roof_pw, "roofline_hbm": roof_hbm,
+            "roofline": roof if a.dtype == "f32" or roof is None else dict(roof_hbm, mfma_conv3=roof), "roofline_pw": roof_pw, "roofline_hbm": roof_hbm,
             "cpu_baseline": cpu,
             "bf16_mode": bf16,
             "inference_1024": infer,
@@ -610,7 +653,7 @@ PMC_TRAFFIC_FILE = "profiles/r04_z_pmc_traffic_by_family.json"
 
 def pmc_traffic(family):
     """HBM bytes per launch of a kernel family ("conv3x", "conv3", "pw") from the committed rocprofv3 PMC passes
-    (written by tools/pmc_family_traffic.py from separate FETCH_SIZE / WRITE_SIZE runs of `bench.py --steps 1 --single-stream`,
+    (written by tools/pmc_family_traffic.py from separate FETCH_SIZE / WRITE_SIZE runs of `bench.py --full --steps 1 --single-stream`,
     gfx950 x2 read correction); counters cannot be read from inside this process, so this is null if the summary is absent."""
     try:
         d = json.load(open(os.path.join(ROOT, PMC_TRAFFIC_FILE)))

@@ -38,6 +38,33 @@ torch.manual_seed(0)
 torch.set_num_threads(8)
 
 
+def save_fixture(name, out, limit=1 << 20, budget=900_000):
+    """tests/golden/<name>.npz, or <name>.part0.npz, <name>.part1.npz, ... when one file would reach `limit` (no committed
+    file may); tests/conftest.py's `golden` fixture reads either form"""
+    import glob
+    import zipfile
+    for old in glob.glob(os.path.join(GOLD, glob.escape(name) + ".npz")) + glob.glob(os.path.join(GOLD, glob.escape(name) + ".part*.npz")):
+        os.remove(old)
+    path = os.path.join(GOLD, name + ".npz")
+    np.savez_compressed(path, **out)
+    if os.path.getsize(path) < limit:
+        return
+    with zipfile.ZipFile(path) as z:
+        cost = {i.filename[:-4]: i.compress_size + 2 * len(i.filename) + 200 for i in z.infolist()}
+    os.remove(path)
+    groups, used = [[]], 0
+    for k in out:
+        if groups[-1] and used + cost[k] > budget:
+            groups.append([])
+            used = 0
+        groups[-1].append(k)
+        used += cost[k]
+    for i, ks in enumerate(groups):
+        part = os.path.join(GOLD, f"{name}.part{i}.npz")
+        np.savez_compressed(part, **{k: out[k] for k in ks})
+        assert os.path.getsize(part) < limit, part
+
+
 class KinkMargin:
     """Smallest distance of any non-smooth point's argument from its kink over one forward of a reference
     model: PReLU / ReLU / LeakyReLU inputs from 0 and the runner-up gap of a channel max (SpatialAttention,
@@ -209,7 +236,7 @@ def gen_hvi():
     assert abs(ka[0] - 0.3712552) < 1e-6 and abs(ka[1] - 0.6430328) < 1e-6 and abs(ka[2] - .8) < 1e-7, ka
     blk = fresh.PHVIT(torch.tensor([1., -2e-8, .5]).reshape(1, 3, 1, 1)).flatten().tolist()
     assert blk == [0.0, 0.0, 0.0], blk
-    np.savez_compressed(os.path.join(GOLD, "hvi_transform.npz"), **out)
+    save_fixture("hvi_transform", out)
     print("wrote hvi_transform.npz", len(out), "arrays")
 
 
@@ -303,7 +330,7 @@ def gen_blocks():
                     f"up_{tag}_g.prelu.weight": up.prelu.weight.grad.numpy(),
                     f"up_{tag}_g.up_scale.0.weight": up.up_scale[0].weight.grad.numpy(),
                     f"up_{tag}_g.up.weight": up.up.weight.grad.numpy()})
-    np.savez_compressed(os.path.join(GOLD, "blocks.npz"), **out)
+    save_fixture("blocks", out)
     print("wrote blocks.npz", len(out), "arrays")
 
 
@@ -358,7 +385,7 @@ def gen_model():
     out["model_c1_out_strided"] = yr[:, :, ::16, ::16].numpy()
     out["model_c1_out_sums"] = np.array([yr.double().sum().item(), yr.double().abs().sum().item(),
                                          (yr.double() ** 2).sum().item()])
-    np.savez_compressed(os.path.join(GOLD, "model.npz"), **out)
+    save_fixture("model", out)
     print("wrote model.npz", len(out), "arrays")
 
 
@@ -411,7 +438,7 @@ def gen_mssa():
         out[f"model_g.{n}"] = prm.grad.numpy()
     print(f"  ok  CIDNet_MSSA grads: worst rel-to-max diff oracle vs reference {worst:.2e}")
     assert worst < 1e-4
-    np.savez_compressed(os.path.join(GOLD, "mssa.npz"), **out)
+    save_fixture("mssa", out)
     print("wrote mssa.npz", len(out), "arrays")
 
 
@@ -487,7 +514,7 @@ def gen_tnsm():
             out[f"model_g64.{n}"] = v.grad.numpy().astype(np.float32)
     print(f"  ok  CIDNet_TNSM grads: worst rel-to-max diff {worst:.2e}; {len(dead)} dead tensors (I_LCA5.*, I_TNSM5.*)")
     assert worst < 1e-4
-    np.savez_compressed(os.path.join(GOLD, "tnsm.npz"), **out)
+    save_fixture("tnsm", out)
     print("wrote tnsm.npz", len(out), "arrays")
 
 
@@ -515,7 +542,7 @@ def gen_losses():
             out[f"{tag}_w{weight}_loss"] = np.float64(lr.item())
             out[f"{tag}_w{weight}_grad"] = xr.grad.numpy()
         out[f"{tag}_x"], out[f"{tag}_y"] = x.numpy(), y.numpy()
-    np.savez_compressed(os.path.join(GOLD, "losses.npz"), **out)
+    save_fixture("losses", out)
     print("wrote losses.npz", len(out), "arrays")
 
 
@@ -543,7 +570,7 @@ def gen_lr_schedule():
         out[tag + "_cfg"] = np.array([lr, n_ep, warm, start, float(use_warm)])
         out[tag + "_lr"] = np.array(seq, dtype=np.float64)
         print(f"  {tag}: lr[0..5] = {seq[:6]}, last = {seq[-1]:.3e}")
-    np.savez_compressed(os.path.join(GOLD, "lr_schedule.npz"), **out)
+    save_fixture("lr_schedule", out)
     print("wrote lr_schedule.npz")
 
 
@@ -677,7 +704,7 @@ def gen_fullsize():
     y64, f64 = O.cidnet_tnsm_forward(p64, x.double())
     ((y64 - gt.double()).abs().mean() + 0.1 * f64.mean()).backward()
     _store_grads(out, "tnsm64", [(n, v.grad.float()) for n, v in p64.items() if v.grad is not None])
-    np.savez_compressed(os.path.join(GOLD, "fullsize.npz"), **out)
+    save_fixture("fullsize", out)
     print("wrote fullsize.npz", len(out), "arrays")
 
 
@@ -752,7 +779,7 @@ def gen_round3():
     out["tnsm400_out_sums"] = np.array([yd.sum().item(), yd.abs().sum().item(), (yd ** 2).sum().item()])
     print(f"  TNSM 400x600: reference fp32 vs fp64 oracle: rgb {(yt.double() - y64).abs().max().item():.2e}, "
           f"noise {(ft.double() - f64).abs().max().item():.2e}")
-    np.savez_compressed(os.path.join(GOLD, "round3.npz"), **out)
+    save_fixture("round3", out)
     print("wrote round3.npz", len(out), "arrays")
 
 
@@ -812,7 +839,7 @@ def gen_round4():
         out[f"{tag}64_out_strided"] = (r64[0] if variant == "tnsm" else r64).detach()[:, :, ::8, ::8].float().numpy()
         print(f"  {tag}: fp64 evaluation done")
         del p64, x64, r64
-    np.savez_compressed(os.path.join(GOLD, "round4.npz"), **out)
+    save_fixture("round4", out)
     print("wrote round4.npz", len(out), "arrays")
 
 

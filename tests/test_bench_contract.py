@@ -61,3 +61,37 @@ def test_work_formulas_follow_the_header_argument_order():
     for n in called:
         nargs = len(protos[n][1])
         assert b.pw_work(n, tuple([0] * nargs)) is not None, f"bench.pw_work does not price {n}"
+
+
+def test_restart_and_dump_outputs(tmp_path):
+    """--dump-outputs: after restart() the steps compute what the same steps of a fresh trainer compute, however many set-up
+    steps ran before it, and dump_outputs() writes the last step's loss, gradients and parameters as float32 .npy files"""
+    import numpy as np
+    import torch
+    from hvi_cidnet_amd.dp import DataParallelTrainer
+    b = _bench()
+
+    def trainer():
+        torch.manual_seed(0)
+        m = torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3, padding=1), torch.nn.PReLU(), torch.nn.Conv2d(8, 3, 1))
+        return m, DataParallelTrainer(m, lr=1e-3, use_hip_kernels=False, loss_fn=lambda y, t: (y - t).abs().mean())
+    g = torch.Generator().manual_seed(1)
+    x, gt = torch.rand((2, 3, 16, 16), generator=g), torch.rand((2, 3, 16, 16), generator=g)
+    outs = []
+    for n_setup in (0, 5):
+        m, tr = trainer()
+        init = [p.detach().cpu() for p in m.parameters()]
+        for _ in range(n_setup):
+            tr.step(x, gt)
+        if n_setup:
+            b.restart(tr, init)
+        for _ in range(3):
+            loss = tr.step(x, gt)
+        d = tmp_path / str(n_setup)
+        b.dump_outputs(str(d), tr, loss)
+        outs.append({n: np.load(d / (n + ".npy")) for n in ("loss", "grads", "params")})
+    fresh, restarted = outs
+    assert fresh["loss"].shape == (1,) and fresh["params"].shape == (sum(p.numel() for p in m.parameters()),)
+    for n in ("loss", "grads", "params"):
+        assert fresh[n].dtype == np.float32
+        assert np.array_equal(fresh[n], restarted[n]), n

@@ -48,7 +48,7 @@ kernels = collections.OrderedDict((short(k), {"launches": fn[k], "avg_hbm_bytes_
                                               "avg_fetch_kib": round(f[k] / max(fn[k], 1), 1), "avg_write_kib": round(w.get(k, 0.0) / max(fn[k], 1), 1)})
                                   for k in top)
 allf, allw = sum(f.values()), sum(w.values())
-json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace), python3 bench.py --steps 1 --warmup 1 "
+json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace), python3 bench.py --full --steps 1 --warmup 1 "
                      "--no-cpu-baseline --no-inference-leg --single-stream (all launches of the process: set-up steps, 1 warm-up, 1 timed, 2 instrumented)",
            "correction": "hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024  (gfx950 FETCH_SIZE reports half of wide coalesced reads); raw_bytes = (FETCH + WRITE) * 1024",
            "families": fam,

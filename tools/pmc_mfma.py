@@ -51,7 +51,7 @@ for name, f in sorted(fam.items(), key=lambda kv: -kv[1]["ns"]):
         for k in ("SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY"):
             if k in f: row[k.lower() + "_per_wave_cycle"] = round(f[k] / f["SQ_WAVE_CYCLES"], 4)
     rows.append(row)
-json.dump({"source": "rocprofv3 --kernel-trace --pmc <SQ counters> -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --single-stream "
+json.dump({"source": "rocprofv3 --kernel-trace --pmc <SQ counters> -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --single-stream "
                      "(tools/pmc_mfma.sh); counter pass only, no --stats",
            "calibration": {"kernel": "tools/mfma_peak.hip (pure v_mfma_f32_16x16x4_f32, 0.987 of peak)",
                            "mfma_busy_counter_per_ns_at_full_rate": full, "top_rates": [round(r[0], 3) for r in rates[:4]]},

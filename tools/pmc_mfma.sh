@@ -15,7 +15,7 @@ echo "counters:$HAVE"
 grep -i -E "mfma" $O/counters_all.txt | cut -c1-160 | sort -u | head -40 > $O/counters_mfma.txt || true
 rocprofv3 --kernel-trace --pmc $HAVE -d $O/cal -o b --output-format csv -- $R/tools/bin/mfma_peak > $O/cal.log 2>&1
 echo "calibration pass done"
-rocprofv3 --kernel-trace --pmc $HAVE -d $O/step -o b --output-format csv -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --single-stream > $O/step.log 2>&1
+rocprofv3 --kernel-trace --pmc $HAVE -d $O/step -o b --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --single-stream > $O/step.log 2>&1
 echo "step pass done"
 python3 $R/tools/pmc_mfma.py $O/cal $O/step $O/pmc_mfma_summary.json
 rm -f $O/counters_all.txt
