@@ -7,7 +7,7 @@ zero_grad, backward, Adam.step) for N ranks:
 
   * parameters live in ONE flat fp32 buffer (the modules' Parameters are views into it); weight
     gradients are written by the HIP backward kernels straight into the matching flat gradient
-    buffer (ops.set_grad_arena), so there is no per-tensor packing before communication;
+    buffer (the trainer's ops.grad_arena), so there is no per-tensor packing before communication;
   * the flat gradient buffer is cut into `n_buckets` contiguous buckets.  Parameters are laid out
     in the order in which their gradients become ready (learned from one probing backward), so
     bucket b is complete while the backward of earlier layers is still running; its all-reduce is
@@ -26,6 +26,7 @@ from __future__ import annotations
 
 from typing import Callable, List, Optional
 
+import contextlib
 import os
 
 import torch
@@ -142,6 +143,9 @@ class DataParallelTrainer:
         self.use_graph = use_graph
         self._graph = None
         self._capturing = False
+        # gradient arena and prepared-weight cache of this trainer (set up in _setup), installed for its passes only
+        self._arena = None
+        self._prep = None
         self.params = [p for p in model.parameters() if p.requires_grad]
 
     # ---- one-time setup: probe gradient order, flatten, hook -----------------------------------
@@ -159,13 +163,13 @@ class DataParallelTrainer:
         ln_uses = [m._use for m in self.model.modules() if hasattr(m, "_use")] if self.use_hip else []
         if self.use_hip:
             from . import ops
-            ops.set_grad_arena(None, None)
             ops.start_grad_probe()
             for st in ln_uses:
                 st.acc, st.fwd, st.bwd, st.probe = False, 0, 0, [0, 0]
         self.model.zero_grad(set_to_none=True)
-        loss = self._loss(self.model(x), gt, x)
-        loss.backward()
+        with self._pass_scope():                    # no arena, no cache yet
+            loss = self._loss(self.model(x), gt, x)
+            loss.backward()
         for h in hooks:
             h.remove()
         # a parameter whose gradient is produced by several kernel launches per step (LayerNorm affine:
@@ -228,13 +232,13 @@ class DataParallelTrainer:
         multi = [p.data_ptr() for p in live if id(p) in multi_ids]      # pointers AFTER re-homing into flat_p
         if self.use_hip:
             from . import ops
-            ops.set_grad_arena(self.flat_p, self.flat_g, exclude_ptrs=multi)
+            self._arena = ops.grad_arena(self.flat_p, self.flat_g, exclude_ptrs=multi)
             ops.enable_wgrad_stream(self.wgrad_stream)
             # this trainer's fused Adam is the only writer of flat_p: inside its passes (_pass_scope) prepared (split,
-            # fragment-ordered) weight operands are kept across launches, and re-prepared in two launches after every update
-            # (ops.refresh_prepared_weights); anything else that writes the weights without torch's version counter seeing
-            # it (p.data.copy_, raw kernels) must call weights_changed()
-            ops.clear_prepared_weights()
+            # fragment-ordered) weight operands are kept across launches in its own cache, and re-prepared in two launches
+            # after every update (_weights_changed); anything else that writes the weights without torch's version counter
+            # seeing it (p.data.copy_, raw kernels) must call weights_changed()
+            self._prep = ops.PreparedWeights() if self.prepared_weights else None
         for p in live:
             p.register_post_accumulate_grad_hook(self._on_grad)
         self.opt = FlatAdam(self.flat_p, kernel=self.use_hip, **self._opt_args)
@@ -349,11 +353,11 @@ class DataParallelTrainer:
         loss.backward(gradient=one)
 
     def _pass_scope(self):
-        if self.use_hip and self.prepared_weights:
-            from . import ops
-            return ops.prepared_weights(True)
-        import contextlib
-        return contextlib.nullcontext()
+        """this trainer's arena and prepared-weight cache, installed for one pass; the previous ones come back after it"""
+        if not self.use_hip:
+            return contextlib.nullcontext()
+        from . import ops
+        return ops.installed(self._arena, self._prep)
 
     def _loss(self, out, gt, x):
         """loss_fn(model(x), gt); a loss function with a true `wants_input` attribute (losses.CIDNetLoss: the TNSM noise terms
@@ -393,10 +397,18 @@ class DataParallelTrainer:
                 self._join_wgrad_stream()
                 self._gloss = loss.detach()
             self._graph = g
+            self._graph_clears = self._prep.clears if self._prep is not None else 0
         finally:
             self._capturing = False
 
     def _graph_step(self, x, gt):
+        # the graph reads the prepared operands' buffers: recapture once they were dropped, and re-prepare them when a
+        # weight was written through torch since the last step (load_state_dict)
+        if self._graph is not None and self._prep is not None:
+            if self._prep.clears != self._graph_clears:
+                self._graph = None
+            elif self._prep.stale():
+                self._prep.refresh(self.flat_p.device)
         if self._graph is None:
             self._capture(x, gt)
         self._gx.copy_(x)
@@ -439,9 +451,8 @@ class DataParallelTrainer:
         return loss
 
     def _weights_changed(self):
-        if self.use_hip and self.prepared_weights and self.flat_p.is_cuda:
-            from . import ops
-            ops.refresh_prepared_weights(self.flat_p.device)
+        if self._prep is not None and self.flat_p.is_cuda:
+            self._prep.refresh(self.flat_p.device)
 
     def weights_changed(self):
         """call after anything that writes the parameters outside torch's version tracking (p.data.copy_, raw kernels): the

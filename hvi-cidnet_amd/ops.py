@@ -4,6 +4,7 @@ Every op launches hand-written HIP kernels on the caller's current stream throug
 provides device memory, the stream and the autograd tape.  Inputs must be fp32 tensors on a ROCm
 device -- anything else raises (no CPU / ATen fallback exists in this package).
 """
+import contextlib
 import ctypes
 import os
 
@@ -304,107 +305,122 @@ def _pe(t, off_elems=0):
 # The split-product kernels (csrc/pwx.hip, csrc/conv3x.hip) read their weights split into bf16 levels in MFMA fragment
 # order.  Preparing them per call costs a 5 us launch in front of every conv: ~125 per training step (98 shared-weight
 # 1x1 convs, 24 dense 3x3 convs; forward and backward use different orders of the same weights), latency the branch
-# streams cannot hide behind anything.  With the cache ON a prepared operand lives in its own buffer, keyed by (weight
-# address, strides, shape, orientation): the first use prepares it, and whoever changes the weights re-prepares ALL of them
-# in two launches (refresh_prepared_weights: one batched kernel per family) -- dp.DataParallelTrainer does after its fused
-# Adam update, which is the only writer of the flat parameter buffer.  An entry also remembers the tensor's autograd
-# version counter, so in-place updates through torch (load_state_dict, torch.optim) are seen and re-prepared on use;
-# writes through `.data` or raw pointers are not -- hence OFF unless a caller that owns the weight updates turns it on
-# (enable_prepared_weights).  Per-sample operands (the attention maps) are never cached.
+# streams cannot hide behind anything.  A PreparedWeights cache keeps every prepared operand in its own buffer, keyed by
+# (weight address, strides, shape, orientation): the first use prepares it, and whoever changes the weights re-prepares ALL
+# of them in two launches (refresh: one batched kernel per family).  An entry also remembers the tensor's autograd version
+# counter, so in-place updates through torch (load_state_dict, torch.optim) are seen and re-prepared on use; writes through
+# `.data` or raw pointers are not -- hence a cache is consulted only while the owner of the weight updates has installed it.
+# The op layer reads one active cache (_PREP["on"]; None: prepare per call).  dp.DataParallelTrainer owns a cache of its
+# own, installs it for its own passes only (installed) and refreshes it after its fused Adam update, the only writer of its
+# flat parameter buffer.  Callers without a trainer (frozen weights) use the module default cache _PREP_DEFAULT through
+# prepared_weights() / enable_prepared_weights().  Per-sample operands (the attention maps) are never cached.
 class _Prepared:
     __slots__ = ("buf", "kind", "row", "version", "tensor")
 
 
-_PREP = {"on": False, "entries": {}, "tables": {}, "stats": [0, 0]}
 # kernel families with a prepared weight operand: cache kind -> prefix of their _prep / _prep_blocks / _prep_batch entry points
 _PREP_FAMILY = {"pw": "cidnet_pw_conv_bf16x3", "c3": "cidnet_conv3x3_bf16x3"}
 _PREP_MAX_ENTRIES = 1024
 
 
+class PreparedWeights:
+    """one cache of prepared weight operands: the entries and the batch tables of refresh()"""
+
+    def __init__(self):
+        self.entries = {}
+        self.tables = {}
+        self.clears = 0             # clear() calls: a captured graph reads the entries' buffers and must not outlive them
+
+    def clear(self):
+        if self.entries and torch.cuda.is_initialized():
+            torch.cuda.synchronize()                             # a refresh or a reader may still be in flight
+        self.entries.clear()
+        self.tables.clear()
+        self.clears += 1
+
+    def stale(self):
+        """whether a weight was written through torch (version counter) since its operand was last prepared"""
+        return any(e.version != e.tensor._version for e in self.entries.values())
+
+    def refresh(self, device=None):
+        """Re-prepare every cached operand from the current weights: one launch per kernel family on the current stream."""
+        if not self.entries:
+            return
+        by = {}
+        for e in self.entries.values():
+            if device is None or e.buf.device == device:
+                by.setdefault((e.kind, e.buf.device), []).append(e)
+        for (kind, dev), es in by.items():
+            tab = self.tables.get((kind, dev))
+            if tab is None:
+                blocks_of = lib().raw(_PREP_FAMILY[kind] + "_prep_blocks")
+                rows, first = [], 0
+                for e in es:
+                    r = list(e.row)
+                    r[6] = first
+                    first += int(blocks_of(r[2], r[3]))
+                    rows.append(r)
+                tab = (torch.tensor(rows, dtype=torch.int64).to(dev), len(rows), first)
+                self.tables[(kind, dev)] = tab
+            t, n, total = tab
+            with torch.cuda.device(dev):
+                lib().call(_PREP_FAMILY[kind] + "_prep_batch", _p(t), n, total, _stream())
+            for e in es:
+                e.version = e.tensor._version
+
+
+_PREP_DEFAULT = PreparedWeights()       # the cache of callers without a trainer
+# "on": the cache the op layer consults (installed() / prepared_weights() / enable_prepared_weights(); None: none);
+# "stats": hits and misses of every cache
+_PREP = {"on": None, "stats": [0, 0]}
+
+
 def clear_prepared_weights():
-    if _PREP["entries"] and torch.cuda.is_initialized():
-        torch.cuda.synchronize()                                 # a refresh or a reader may still be in flight
-    _PREP["entries"].clear()
-    _PREP["tables"].clear()
+    _PREP_DEFAULT.clear()
 
 
 def enable_prepared_weights(on=True):
-    """global switch; switching (on or off) drops every cached operand"""
-    clear_prepared_weights()
-    _PREP["on"] = bool(on)
+    """switch the default cache on or off outside any installed() block; switching drops every operand it holds"""
+    _PREP_DEFAULT.clear()
+    _PREP["on"] = _PREP_DEFAULT if on else None
 
 
-class prepared_weights:
-    """`with ops.prepared_weights(True): ...` -- the cache is consulted only inside the block (entries survive it): the
-    trainer wraps its own forward+backward passes, so a model(x) call outside them (validation, a user's own weight
-    surgery between steps) prepares per call as ever."""
+def prepared_weights(on=True):
+    """`with ops.prepared_weights(True): ...` -- the default cache is consulted only inside the block (entries survive it)"""
+    return installed(_ARENA, _PREP_DEFAULT if on else None)
 
-    def __init__(self, on=True):
-        self.on = bool(on)
 
-    def __enter__(self):
-        self.prev = _PREP["on"]
-        _PREP["on"] = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _PREP["on"] = self.prev
-        return False
+def refresh_prepared_weights(device=None):
+    """re-prepare the default cache after its weights changed behind torch's back"""
+    _PREP_DEFAULT.refresh(device)
 
 
 def _prepared(kind, w, w_off, w_ms, w_ks, flip, M, K, n_floats, prepare):
-    """-> buffer holding the prepared operand of weight view (w, w_off, strides), or None with the cache off"""
-    if not _PREP["on"]:
+    """-> buffer holding the prepared operand of weight view (w, w_off, strides), or None with no cache installed"""
+    c = _PREP["on"]
+    if c is None:
         return None
     src = w.data_ptr() + 4 * int(w_off)
     key = (kind, src, int(w_ms), int(w_ks), int(flip), M, K)
-    e = _PREP["entries"].get(key)
+    e = c.entries.get(key)
     ver = w._version
     if e is not None and e.version == ver:
         _PREP["stats"][0] += 1
         return e.buf
     _PREP["stats"][1] += 1
     if e is None:
-        if len(_PREP["entries"]) >= _PREP_MAX_ENTRIES:          # weights re-homed over and over: start again
-            _PREP["entries"].clear()
+        if len(c.entries) >= _PREP_MAX_ENTRIES:                 # weights re-homed over and over: start again
+            c.clear()
         e = _Prepared()
         e.buf = torch.empty(int(n_floats), device=w.device, dtype=torch.float32)
         e.kind = kind
         e.row = (src, e.buf.data_ptr(), M, K, int(w_ms), int(w_ks), 0, int(flip))
         e.tensor = w
-        _PREP["entries"][key] = e
-        _PREP["tables"].pop((kind, w.device), None)
+        c.entries[key] = e
+        c.tables.pop((kind, w.device), None)
     e.version = ver
     prepare(e.buf)
     return e.buf
-
-
-def refresh_prepared_weights(device=None):
-    """Re-prepare every cached operand from the current weights: one launch per kernel family on the current stream.  For
-    the owner of the weight updates (dp.DataParallelTrainer calls it right after the optimizer step)."""
-    if not _PREP["entries"]:
-        return
-    by = {}
-    for e in _PREP["entries"].values():
-        if device is None or e.buf.device == device:
-            by.setdefault((e.kind, e.buf.device), []).append(e)
-    for (kind, dev), es in by.items():
-        tab = _PREP["tables"].get((kind, dev))
-        if tab is None:
-            blocks_of = lib().raw(_PREP_FAMILY[kind] + "_prep_blocks")
-            rows, first = [], 0
-            for e in es:
-                r = list(e.row)
-                r[6] = first
-                first += int(blocks_of(r[2], r[3]))
-                rows.append(r)
-            tab = (torch.tensor(rows, dtype=torch.int64).to(dev), len(rows), first)
-            _PREP["tables"][(kind, dev)] = tab
-        t, n, total = tab
-        with torch.cuda.device(dev):
-            lib().call(_PREP_FAMILY[kind] + "_prep_batch", _p(t), n, total, _stream())
-        for e in es:
-            e.version = e.tensor._version
 
 
 _BILINEAR_TABS = {}
@@ -1449,17 +1465,39 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=
 
 # --------------------------------------------------------------------------------------------
 # gradient arena: weight gradients are written straight into one flat buffer (the all-reduce /
-# optimizer operand) instead of 191 separately allocated tensors
+# optimizer operand) instead of 191 separately allocated tensors.  The op layer reads the active
+# arena and the active prepared-weight cache from plain module globals: the backward runs on
+# autograd's device threads, which thread-locals and context variables do not reach.  A trainer
+# installs its own arena and cache for its own passes only (installed), so several trainers
+# coexist on one thread.
 # --------------------------------------------------------------------------------------------
 _ARENA = None
 
 
+def grad_arena(flat_p, flat_g, exclude_ptrs=()):
+    """-> the arena installed() takes: parameters must be views into `flat_p`; their gradients are then
+    produced as the matching views of `flat_g`.  `exclude_ptrs`: data_ptr()s of parameters used more
+    than once per step (their gradients must be accumulated by autograd instead)."""
+    return None if flat_p is None else (flat_p.data_ptr(), flat_p.numel(), flat_g, frozenset(exclude_ptrs))
+
+
 def set_grad_arena(flat_p, flat_g, exclude_ptrs=()):
-    """Parameters must be views into `flat_p`; their gradients are then produced as the matching
-    views of `flat_g`.  `exclude_ptrs`: data_ptr()s of parameters used more than once per step
-    (their gradients must be accumulated by autograd instead)."""
+    """install grad_arena(...) outside any installed() block; (None, None) installs none"""
     global _ARENA
-    _ARENA = None if flat_p is None else (flat_p.data_ptr(), flat_p.numel(), flat_g, frozenset(exclude_ptrs))
+    _ARENA = grad_arena(flat_p, flat_g, exclude_ptrs)
+
+
+@contextlib.contextmanager
+def installed(arena, prepared):
+    """install a gradient arena (grad_arena(), or None) and a prepared-weight cache (PreparedWeights, or None) for the
+    block; the previous ones come back on exit, also on an exception"""
+    global _ARENA
+    prev = _ARENA, _PREP["on"]
+    _ARENA, _PREP["on"] = arena, prepared
+    try:
+        yield
+    finally:
+        _ARENA, _PREP["on"] = prev
 
 
 _GL_COUNT = None      # {data_ptr: number of grad_like() calls}: probe for parameters used more than once

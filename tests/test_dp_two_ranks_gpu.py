@@ -96,7 +96,6 @@ def test_two_ranks_on_one_gpu_match_single_process(precision):
     # single process, concatenated batch (mean loss over the global batch = mean of the per-rank means)
     sys.path.insert(0, ROOT)
     from hvi_cidnet_amd.dp import DataParallelTrainer
-    from hvi_cidnet_amd import ops
     import hvi_cidnet_amd as P
     P.set_precision(precision)
     try:
@@ -108,8 +107,5 @@ def test_two_ranks_on_one_gpu_match_single_process(precision):
         ref = tr.flat_g[:tr.n_live].cpu()
     finally:
         P.set_precision("f32")
-        ops.clear_prepared_weights()
-        ops.set_grad_arena(None, None)
-        ops.enable_wgrad_stream(False)
     d = (res[0][0] - ref).abs().max().item()
     assert d <= 2e-5 * ref.abs().max().item() + 1e-9, (d, ref.abs().max().item())

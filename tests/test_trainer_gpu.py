@@ -9,6 +9,18 @@ from oracle import cidnet_oracle as O
 pytestmark = pytest.mark.gpu
 
 
+def _foreign_kernels():
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    try:
+        from foreign_kernels_in_step import foreign_kernels
+    finally:
+        sys.path.pop(0)
+    return foreign_kernels
+
+
 def _model(dev, chans):
     import hvi_cidnet_amd as P
     m = P.CIDNet(channels=list(chans))
@@ -24,8 +36,6 @@ def test_trainer_gradients_and_update_match_plain_autograd(dev, chans, shape):
     x = O.synthetic_batch(31, shape).to(dev)
     gt = O.synthetic_batch(32, shape).to(dev)
     # plain autograd reference (no arena, single stream)
-    ops.set_grad_arena(None, None)
-    ops.enable_wgrad_stream(False)
     ref = _model(dev, chans)
     ref.two_streams = False
     loss_r = ops.L1LossFn.apply(ref(x), gt)
@@ -61,8 +71,6 @@ def test_trainer_gradients_and_update_match_plain_autograd(dev, chans, shape):
     # one full step == torch Adam fed with the harness's own gradients.  (Fed with the plain-autograd gradients
     # instead, first-step Adam ~ lr * g / (|g| + eps) amplifies summation-order noise on elements with
     # |g| ~ eps into differences of the order of lr, so that comparison would test luck.)
-    ops.set_grad_arena(None, None)
-    ops.enable_wgrad_stream(False)
     m2 = _model(dev, chans)
     before = {n: p.detach().clone() for n, p in m2.named_parameters()}
     tr2 = DataParallelTrainer(m2, lr=1e-3, n_buckets=3)
@@ -82,8 +90,6 @@ def test_trainer_gradients_and_update_match_plain_autograd(dev, chans, shape):
     torch.optim.Adam([t for _, _, t in twins], lr=1e-3).step()
     for n, p, t in twins:
         assert torch.allclose(p, t, atol=1e-7, rtol=1e-6), n
-    ops.set_grad_arena(None, None)
-    ops.enable_wgrad_stream(False)
 
 
 def test_trainer_survives_stray_grad_mode_forward(dev):
@@ -97,8 +103,6 @@ def test_trainer_survives_stray_grad_mode_forward(dev):
     chans, shape = (12, 12, 24, 48), (2, 3, 32, 48)
     x = O.synthetic_batch(41, shape).to(dev)
     gt = O.synthetic_batch(42, shape).to(dev)
-    ops.set_grad_arena(None, None)
-    ops.enable_wgrad_stream(False)
     ref = _model(dev, chans)
     ref.two_streams = False
     ops.L1LossFn.apply(ref(x), gt).backward()
@@ -122,8 +126,6 @@ def test_trainer_survives_stray_grad_mode_forward(dev):
         err = (got - grads[n]).abs().max().item()
         assert err <= 1e-5 * grads[n].abs().max().item() + 1e-8, f"{n}: {err:.3e}"
     del y_stray
-    ops.set_grad_arena(None, None)
-    ops.enable_wgrad_stream(False)
 
 
 def test_model_deepcopy_and_save_after_forward(dev, tmp_path):
@@ -145,21 +147,16 @@ def test_trainer_rccl_path_on_one_rank(dev, monkeypatch):
     stream, 1/world folded into Adam) exercised on ONE rank over RCCL: a 1-rank all-reduce is the identity, so
     gradients and the update must equal the no-communication run bit for bit."""
     import torch.distributed as dist
-    from hvi_cidnet_amd import ops
     from hvi_cidnet_amd.dp import DataParallelTrainer
     chans, shape = (12, 12, 24, 48), (2, 3, 32, 48)
     x = O.synthetic_batch(41, shape).to(dev)
     gt = O.synthetic_batch(42, shape).to(dev)
-    ops.set_grad_arena(None, None)
-    ops.enable_wgrad_stream(False)
     m0 = _model(dev, chans)
     t0 = DataParallelTrainer(m0, lr=1e-3, n_buckets=3)
     t0.step(x, gt)
     torch.cuda.synchronize()
     ref_g = t0.flat_g.clone()
     ref_p = t0.flat_p.clone()
-    ops.set_grad_arena(None, None)
-    ops.enable_wgrad_stream(False)
     monkeypatch.setenv("CIDNET_DP_FORCE_ALLREDUCE", "1")
     dist.init_process_group(backend="nccl", init_method="tcp://127.0.0.1:29571", world_size=1, rank=0)
     try:
@@ -172,8 +169,6 @@ def test_trainer_rccl_path_on_one_rank(dev, monkeypatch):
         assert torch.equal(t1.flat_p, ref_p)
     finally:
         dist.destroy_process_group()
-        ops.set_grad_arena(None, None)
-        ops.enable_wgrad_stream(False)
 
 
 @pytest.mark.parametrize("chans,shape", [((12, 12, 24, 48), (2, 3, 32, 48)), ((36, 36, 72, 144), (1, 3, 64, 96))])
@@ -182,20 +177,15 @@ def test_trainer_graph_replay_equals_eager(dev, chans, shape):
     gradients and parameter updates bit for bit, step after step (new inputs are copied into the static buffers).  The
     full-width case runs the split-product kernels inside the capture: their prepared weight operands are cache hits there
     (created by the eager passes before the capture) and are refreshed after every Adam update outside the graph."""
-    from hvi_cidnet_amd import ops
     from hvi_cidnet_amd.dp import DataParallelTrainer
     batches = [(O.synthetic_batch(51 + i, shape).to(dev), O.synthetic_batch(61 + i, shape).to(dev)) for i in range(3)]
     res = []
     for use_graph in (False, True):
-        ops.set_grad_arena(None, None)
-        ops.enable_wgrad_stream(False)
         m = _model(dev, chans)
         tr = DataParallelTrainer(m, lr=1e-3, n_buckets=3, use_graph=use_graph)
         losses = [float(tr.step(x, gt).item()) for x, gt in batches]
         torch.cuda.synchronize()
         res.append((losses, tr.flat_g.clone(), tr.flat_p.clone()))
-    ops.set_grad_arena(None, None)
-    ops.enable_wgrad_stream(False)
     assert res[0][0] == res[1][0], (res[0][0], res[1][0])
     assert torch.equal(res[0][1], res[1][1])
     assert torch.equal(res[0][2], res[1][2])
@@ -206,10 +196,7 @@ def test_trainer_with_reference_objective(dev):
     without the VGG term): gradients reach every live parameter, including density_k through the loss-side HVIT,
     and a few steps reduce the loss"""
     import hvi_cidnet_amd as P
-    from hvi_cidnet_amd import ops
     from hvi_cidnet_amd.dp import DataParallelTrainer
-    ops.set_grad_arena(None, None)
-    ops.enable_wgrad_stream(False)
     chans, shape = (12, 12, 24, 48), (2, 3, 32, 48)
     m = _model(dev, chans)
     x = O.synthetic_batch(71, shape).to(dev)
@@ -220,8 +207,6 @@ def test_trainer_with_reference_objective(dev):
     assert all(l == l for l in losses), losses
     assert losses[-1] < losses[0], losses
     assert tr.flat_g[:tr.n_live].abs().max().item() > 0
-    ops.set_grad_arena(None, None)
-    ops.enable_wgrad_stream(False)
 
 
 @pytest.mark.parametrize("two_streams", [True, False])
@@ -233,15 +218,8 @@ def test_training_step_launches_only_cidnet_kernels(dev, two_streams):
     L1 loss, backward into the arena, fused Adam -- must launch nothing but cidnet:: kernels (at N > 1: plus RCCL's
     FuncSum kernels, audited in profiles/r04_a_audit_rccl_gfx950_packed_fp32.json): no autograd accumulation adds, no
     slice copies, no fills, no device-to-device memcpy."""
-    import os
-    import sys
     from hvi_cidnet_amd.dp import DataParallelTrainer
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, os.path.join(root, "tools"))
-    try:
-        from foreign_kernels_in_step import foreign_kernels
-    finally:
-        sys.path.pop(0)
+    foreign_kernels = _foreign_kernels()
     chans, shape = (36, 36, 72, 144), (2, 3, 64, 96)
     x = O.synthetic_batch(41, shape).to(dev)
     gt = O.synthetic_batch(42, shape).to(dev)
@@ -264,24 +242,76 @@ def test_trainer_prepared_weights_bit_identical(dev):
     x = O.synthetic_batch(41, shape).to(dev)
     gt = O.synthetic_batch(42, shape).to(dev)
     finals = []
-    try:
-        for prepared in (False, True):
-            m = _model(dev, chans)
-            tr = DataParallelTrainer(m, lr=1e-3, prepared_weights=prepared)
-            ops._PREP["stats"][:] = [0, 0]
-            for _ in range(3):
-                tr.step(x, gt)
-            torch.cuda.synchronize()
-            finals.append(tr.flat_p.clone())
-            if prepared:
-                hits, misses = ops._PREP["stats"]
-                assert misses > 50 and hits >= 2 * misses - 10, (hits, misses)    # prepared in the first pass, reused afterwards
-                assert not ops._PREP["on"]             # the cache is consulted inside the trainer's passes only
-        assert torch.equal(finals[0], finals[1])
-    finally:
-        ops.enable_prepared_weights(False)
-        ops.set_grad_arena(None, None)
-        ops.enable_wgrad_stream(False)
+    for prepared in (False, True):
+        m = _model(dev, chans)
+        tr = DataParallelTrainer(m, lr=1e-3, prepared_weights=prepared)
+        ops._PREP["stats"][:] = [0, 0]
+        for _ in range(3):
+            tr.step(x, gt)
+        torch.cuda.synchronize()
+        finals.append(tr.flat_p.clone())
+        if prepared:
+            hits, misses = ops._PREP["stats"]
+            assert misses > 50 and hits >= 2 * misses - 10, (hits, misses)    # prepared in the first pass, reused afterwards
+            assert not ops._PREP["on"]             # the cache is installed for the trainer's passes only
+    assert torch.equal(finals[0], finals[1])
+
+
+def test_second_trainer_leaves_the_first_alone(dev):
+    """Each trainer installs its gradient arena and prepared-weight cache for its own passes only: a trainer B built and
+    stepped between two steps of trainer A changes nothing in A's next step -- it still launches only cidnet:: kernels
+    (its gradients land in its own arena), and A's parameters and gradients equal those of A run alone bit for bit.
+    Outside a step nothing is installed."""
+    from hvi_cidnet_amd import ops
+    from hvi_cidnet_amd.dp import DataParallelTrainer
+    foreign_kernels = _foreign_kernels()
+    chans, shape = (36, 36, 72, 144), (2, 3, 64, 96)
+    x = O.synthetic_batch(41, shape).to(dev)
+    gt = O.synthetic_batch(42, shape).to(dev)
+    res = []
+    for with_b in (False, True):
+        a = DataParallelTrainer(_model(dev, chans), lr=1e-3)
+        for _ in range(2):
+            a.step(x, gt)
+        if with_b:
+            b = DataParallelTrainer(_model(dev, chans), lr=1e-3)
+            b.step(gt, x)
+            fk = foreign_kernels(a, x, gt, steps=1)
+            assert not fk, {k: [(op, shp) for op, shp, _ in v][:3] for k, v in fk.items()}
+        else:
+            a.step(x, gt)
+        assert ops._ARENA is None and ops._PREP["on"] is None
+        torch.cuda.synchronize()
+        res.append((a.flat_p.clone(), a.flat_g.clone()))
+    assert torch.equal(res[0][0], res[1][0])
+    assert torch.equal(res[0][1], res[1][1])
+
+
+def test_graph_trainer_with_second_trainer_and_load_state_dict(dev):
+    """A captured graph reads the buffers of its trainer's prepared weight operands: a second trainer built and stepped
+    after the capture must not free them, and a load_state_dict into the model after the capture must be re-prepared
+    before the next replay.  The graph trainer's losses, gradients and parameters equal an eager trainer's fed the same
+    sequence bit for bit."""
+    from hvi_cidnet_amd import ops
+    from hvi_cidnet_amd.dp import DataParallelTrainer
+    chans, shape = (36, 36, 72, 144), (2, 3, 64, 96)
+    batches = [(O.synthetic_batch(51 + i, shape).to(dev), O.synthetic_batch(61 + i, shape).to(dev)) for i in range(5)]
+    res = []
+    for use_graph in (False, True):
+        m = _model(dev, chans)
+        init = {k: v.clone() for k, v in m.state_dict().items()}
+        a = DataParallelTrainer(m, lr=1e-3, use_graph=use_graph)
+        losses = [float(a.step(x, gt).item()) for x, gt in batches[:2]]
+        b = DataParallelTrainer(_model(dev, chans), lr=1e-3)
+        b.step(*batches[2])
+        m.load_state_dict(init)                                      # back to the initial weights (Adam moments stay)
+        losses += [float(a.step(x, gt).item()) for x, gt in batches[3:]]
+        assert ops._ARENA is None and ops._PREP["on"] is None
+        torch.cuda.synchronize()
+        res.append((losses, a.flat_g.clone(), a.flat_p.clone()))
+    assert res[0][0] == res[1][0], (res[0][0], res[1][0])
+    assert torch.equal(res[0][1], res[1][1])
+    assert torch.equal(res[0][2], res[1][2])
 
 
 def test_trainer_with_tnsm_model_and_its_objective(dev):
@@ -289,7 +319,6 @@ def test_trainer_with_tnsm_model_and_its_objective(dev):
     losses.CIDNetLoss(tnsm_weight=1) (train_tnsm.py:56-72; options.py:61), whose noise terms then reach the noise branch;
     without a noise map a positive tnsm_weight raises instead of silently dropping the terms."""
     import hvi_cidnet_amd as P
-    from hvi_cidnet_amd import ops
     from hvi_cidnet_amd.dp import DataParallelTrainer
     chans, shape = (12, 12, 24, 48), (2, 3, 32, 48)
     torch.manual_seed(3)
@@ -297,28 +326,23 @@ def test_trainer_with_tnsm_model_and_its_objective(dev):
     x = O.synthetic_batch(51, shape).to(dev)
     gt = O.synthetic_batch(52, shape).to(dev)
     lf = P.CIDNetLoss(m, tnsm_weight=1.0).to(dev)
-    try:
-        with pytest.raises(ValueError, match="noise map"):
-            lf(torch.rand(shape, device=dev), gt)
-        # manual composition of the same objective
-        rgb, noise = m(x)
-        manual = P.CIDNetLoss(m, tnsm_weight=0.0).to(dev)(rgb, gt) + P.tnsm_noise_loss(noise, rgb, x, 1.0)
-        tr = DataParallelTrainer(m, lr=1e-4, loss_fn=lf)
-        loss = tr.forward_backward(x, gt)
-        torch.cuda.synchronize()
-        assert abs(loss.item() - manual.item()) <= 1e-5 * abs(manual.item()) + 1e-6
-        names = {id(p): n for n, p in m.named_parameters()}
-        noise_params = [p for p in tr.params if "noise_map_generator" in names[id(p)] and id(p) in tr._slices
-                        and not names[id(p)].startswith("I_TNSM5")]
-        assert noise_params
-        off, n = tr._slices[id(noise_params[0])]
-        assert tr.flat_g[off:off + n].abs().max().item() > 0
-        l2 = tr.step(x, gt)
-        assert torch.isfinite(l2)
-    finally:
-        ops.clear_prepared_weights()
-        ops.set_grad_arena(None, None)
-        ops.enable_wgrad_stream(False)
+    with pytest.raises(ValueError, match="noise map"):
+        lf(torch.rand(shape, device=dev), gt)
+    # manual composition of the same objective
+    rgb, noise = m(x)
+    manual = P.CIDNetLoss(m, tnsm_weight=0.0).to(dev)(rgb, gt) + P.tnsm_noise_loss(noise, rgb, x, 1.0)
+    tr = DataParallelTrainer(m, lr=1e-4, loss_fn=lf)
+    loss = tr.forward_backward(x, gt)
+    torch.cuda.synchronize()
+    assert abs(loss.item() - manual.item()) <= 1e-5 * abs(manual.item()) + 1e-6
+    names = {id(p): n for n, p in m.named_parameters()}
+    noise_params = [p for p in tr.params if "noise_map_generator" in names[id(p)] and id(p) in tr._slices
+                    and not names[id(p)].startswith("I_TNSM5")]
+    assert noise_params
+    off, n = tr._slices[id(noise_params[0])]
+    assert tr.flat_g[off:off + n].abs().max().item() > 0
+    l2 = tr.step(x, gt)
+    assert torch.isfinite(l2)
 
 
 def test_bf16_mode_training_tracks_fp32(dev):
@@ -327,7 +351,6 @@ def test_bf16_mode_training_tracks_fp32(dev):
     6 % of the fp32 loss at every step (measured: 2.1 %; two Adam trajectories drift apart); parameters stay finite.  Gradient quality is pinned separately against
     fp64 (tests/test_fullsize_gpu.py::test_cidnet_400x600_bf16_mode_vs_reference)."""
     import hvi_cidnet_amd as P
-    from hvi_cidnet_amd import ops
     from hvi_cidnet_amd.dp import DataParallelTrainer
     chans, shape = (36, 36, 72, 144), (2, 3, 64, 96)
     x = (O.synthetic_batch(61, shape) * 0.3).to(dev)           # a dark input ...
@@ -345,9 +368,6 @@ def test_bf16_mode_training_tracks_fp32(dev):
             del tr, m
     finally:
         P.set_precision("f32")
-        ops.clear_prepared_weights()
-        ops.set_grad_arena(None, None)
-        ops.enable_wgrad_stream(False)
     f, b = curves["f32"], curves["bf16"]
     assert f[-1] < 0.9 * f[0] and b[-1] < 0.9 * b[0], (f[0], f[-1], b[0], b[-1])
     worst = max(abs(p - q) / q for p, q in zip(b, f))
