@@ -255,6 +255,13 @@ class CIDNet(nn.Module, _HubMixin):
         q.append(ev)
 
     def forward(self, x):
+        # cat([hv_0, i_dec0], 1) + hvi -> PHVIT, fused (net/CIDNet.py:119-120)
+        return self.trans.PHVIT_residual(*self.trunk(x))
+
+    def trunk(self, x):
+        """Everything of forward() before the output transform: -> (hv_0, i_dec0, hvi), the three inputs of
+        trans.PHVIT_residual.  trans.gated / alpha_s / gated2 / alpha act only inside PHVIT, so an evaluation that sweeps
+        them (metrics.evaluate) runs this once and PHVIT_residual per setting."""
         self._backpressure(x)
         if x.shape[2] % 8 or x.shape[3] % 8:
             raise RuntimeError(f"CIDNet: H and W must be multiples of 8 (got {tuple(x.shape[2:])}); the reference "
@@ -301,9 +308,7 @@ class CIDNet(nn.Module, _HubMixin):
             lambda: self.ID_block0(self._gate("sa_i1", self.ID_block1(i_dec1, i_jump0))),
             lambda: self.HVD_block0(self._gate("sa_hv1", self.HVD_block1(hv_1, hv_jump0))),
             (i_dec1, hv_1, i_jump0, hv_jump0))
-
-        # cat([hv_0, i_dec0], 1) + hvi -> PHVIT, fused (net/CIDNet.py:119-120)
-        return self.trans.PHVIT_residual(hv_0, i_dec0, hvi)
+        return hv_0, i_dec0, hvi
 
     def HVIT(self, x):
         return self.trans.HVIT(x)

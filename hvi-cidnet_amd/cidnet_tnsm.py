@@ -41,9 +41,24 @@ class CIDNet_TNSM(_BaseCIDNet):
         return i_t, hv_t
 
     def forward(self, x):
+        maps = []
+        hv_0, i_dec0, hvi = self._trunk(x, maps)
+        rgb = self.trans.PHVIT_residual(hv_0, i_dec0, hvi)
+        if self.use_tnsm and self.training:
+            if not maps:
+                raise ValueError("noise_maps list is empty during training with use_tnsm=True")
+            stacked = ops.ResizeCatFn.apply(rgb.shape[-2], rgb.shape[-1], *maps)
+            fused = ops.UnaryFn.apply(ops.Conv3x3Fn.apply(stacked, self.noise_fusion[0].weight), "sigmoid")
+            return rgb, fused
+        return rgb, None
+
+    def trunk(self, x):
+        """-> (hv_0, i_dec0, hvi), the inputs of trans.PHVIT_residual (see CIDNet.trunk); the noise maps are dropped"""
+        return self._trunk(x, [])
+
+    def _trunk(self, x, maps):
         if x.shape[2] % 8 or x.shape[3] % 8:
             raise RuntimeError(f"CIDNet_TNSM: H and W must be multiples of 8 (got {tuple(x.shape[2:])})")
-        maps = []
         hvi = self.trans.HVIT(x)
         i = hvi[:, 2:3, :, :].contiguous()
         i_enc0 = self.IE_block0(i)
@@ -71,11 +86,4 @@ class CIDNet_TNSM(_BaseCIDNet):
         i_dec0 = self.ID_block0(i_dec1)
         hv_1 = self.HVD_block1(hv_1, hv_jump0)
         hv_0 = self.HVD_block0(hv_1)
-        rgb = self.trans.PHVIT_residual(hv_0, i_dec0, hvi)
-        if self.use_tnsm and self.training:
-            if not maps:
-                raise ValueError("noise_maps list is empty during training with use_tnsm=True")
-            stacked = ops.ResizeCatFn.apply(rgb.shape[-2], rgb.shape[-1], *maps)
-            fused = ops.UnaryFn.apply(ops.Conv3x3Fn.apply(stacked, self.noise_fusion[0].weight), "sigmoid")
-            return rgb, fused
-        return rgb, None
+        return hv_0, i_dec0, hvi

@@ -1,0 +1,331 @@
+"""Image-quality evaluation on the device: the reference's eval.py (model -> clamped 8-bit output) and measure.py (PSNR,
+SSIM, optionally after the "GT mean" rescale) without the PNG round trip through the host.
+
+    from hvi_cidnet_amd import metrics as M
+    q = M.to_uint8(rgb, size=(h, w))        # fp32 (B,3,Hp,Wp) -> uint8 (B,3,h,w): clamp, x255, truncate, crop
+    p = M.psnr(q, gt_u8, gt_mean=False)     # (B,) float64 on the device, no host synchronisation
+    s = M.ssim(q, gt_u8, gt_mean=False)     # (B,) float64 on the device
+    res = M.evaluate(model, pairs, gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0, batch_size=1)
+    pairs = M.folder_pairs(low_dir, high_dir)
+
+The kernels are csrc/metrics.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
+Differences from the reference scripts, none of which changes a per-image value:
+  * measure.py counts a low image without a ground truth in the divisor of its averages (it skips the image after
+    `n += 1`); here such an image is skipped and reported (FolderPairs.skipped, EvalResult.skipped) and not counted;
+  * eval.py leaves `trans.alpha` (and with it the model's state) as the last run set it; evaluate() restores every
+    attribute it touches and the train / eval mode of every submodule;
+  * a ground truth whose size differs from the output raises (measure.py:134 would bicubic-resize the output);
+  * PSNR sums its squared errors exactly (fp64) where measure.py averages in fp32: < 1e-4 dB apart;
+  * LPIPS is not computed (it needs AlexNet weights and the lpips package's heads).
+"""
+from __future__ import annotations
+
+import os
+import warnings
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+from . import ops
+from ._lib import lib
+from .inference import pad_to_multiple
+
+_NO_CPU = ("hvi-cidnet_amd ops run only on a ROCm device (got a CPU tensor); there is no CPU fallback -- use the oracle "
+           "under oracle/ for CPU checks")
+# measure.py:98-125: the ground truth of `name` is `name` itself in the GT directory, else the same stem with these extensions
+GT_EXTENSIONS = (".jpg", ".JPG", ".jpeg", ".JPEG", ".png", ".PNG")
+_IMAGE_EXTENSIONS = {".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp"}
+
+
+def _on_device(*ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError(_NO_CPU)
+
+
+def _batched(t, what):
+    if t.dim() == 3:
+        t = t.unsqueeze(0)
+    if t.dim() != 4 or t.shape[1] != 3:
+        raise RuntimeError(f"{what}: expected (B,3,H,W) or (3,H,W), got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def to_uint8(rgb: torch.Tensor, size=None) -> torch.Tensor:
+    """fp32 (B,3,Hp,Wp) (or (3,Hp,Wp)) on the device -> uint8 (B,3,h,w): the top-left (h, w) = `size` crop (default the whole
+    image) of trunc(clamp(x, 0, 1) * 255.0f), bit-equal to torch.clamp(x, 0, 1).mul(255).byte() (eval.py:69-73 and
+    ToPILImage).  NaN becomes 0."""
+    _on_device(rgb)
+    if rgb.dtype != torch.float32:
+        raise RuntimeError(f"to_uint8: expected fp32 (got {rgb.dtype})")
+    squeeze = rgb.dim() == 3
+    x = _batched(rgb, "to_uint8")
+    B, _, Hp, Wp = x.shape
+    h, w = (Hp, Wp) if size is None else (int(size[0]), int(size[1]))
+    if not (0 < h <= Hp and 0 < w <= Wp):
+        raise RuntimeError(f"to_uint8: crop {(h, w)} outside the {(Hp, Wp)} image")
+    q = torch.empty((B, 3, h, w), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        lib().call("cidnet_metric_to_uint8", ops._p(x), ops._p(q), B, Hp, Wp, h, w, ops._stream())
+    return q[0] if squeeze else q
+
+
+def psnr_ssim(restored: torch.Tensor, gt: torch.Tensor, gt_mean: bool = False, want_psnr: bool = True,
+              want_ssim: bool = True):
+    """uint8 (B,3,h,w) pairs on the device -> (psnr, ssim), each (B,) float64 on the device (None where not wanted), from one
+    pass over the images.  gt_mean: rescale `restored` by mean(gray(gt)) / mean(gray(restored)) first (measure.py:138-141),
+    on the device.  SSIM needs h, w >= 11."""
+    _on_device(restored, gt)
+    if restored.dtype != torch.uint8 or gt.dtype != torch.uint8:
+        raise RuntimeError(f"psnr / ssim take uint8 images (got {restored.dtype}, {gt.dtype}); see to_uint8")
+    a, g = _batched(restored, "restored"), _batched(gt, "gt")
+    if a.shape != g.shape or a.device != g.device:
+        raise RuntimeError(f"psnr / ssim: restored {tuple(a.shape)} and gt {tuple(g.shape)} differ")
+    B, _, h, w = a.shape
+    if want_ssim and (h < 11 or w < 11):
+        raise RuntimeError(f"ssim needs images of at least 11 x 11 pixels (got {h} x {w}): the 11 x 11 window's valid region "
+                           "would be empty")
+    n = lib().raw("cidnet_metric_ws_floats")(B, h, w)
+    ws = torch.empty(n, dtype=torch.float32, device=a.device)
+    p = torch.empty(B, dtype=torch.float64, device=a.device) if want_psnr else None
+    s = torch.empty(B, dtype=torch.float64, device=a.device) if want_ssim else None
+    with torch.cuda.device(a.device):
+        lib().call("cidnet_metric_psnr_ssim", ops._p(a), ops._p(g), int(bool(gt_mean)), ops._p(p), ops._p(s), ops._p(ws), n,
+                   B, h, w, ops._stream())
+    return p, s
+
+
+def psnr(restored: torch.Tensor, gt: torch.Tensor, gt_mean: bool = False) -> torch.Tensor:
+    """(B,) float64: 10 log10(255^2 / (mean((restored - gt)^2) + 1e-8)) per image (measure.py:66-71)"""
+    return psnr_ssim(restored, gt, gt_mean, want_ssim=False)[0]
+
+
+def ssim(restored: torch.Tensor, gt: torch.Tensor, gt_mean: bool = False) -> torch.Tensor:
+    """(B,) float64: mean over the three colour planes of the mean SSIM map (measure.py:23-64)"""
+    return psnr_ssim(restored, gt, gt_mean, want_psnr=False)[1]
+
+
+# ---- ground truth / input conversion (host side: what PIL, numpy or ToTensor() hand over) ---------------------------------
+def _to_array(img):
+    if isinstance(img, (torch.Tensor, np.ndarray)):
+        return img
+    if hasattr(img, "convert"):                                  # a PIL image
+        return np.array(img.convert("RGB"))
+    return np.asarray(img)
+
+
+def _gt_u8(gt, device) -> torch.Tensor:
+    """-> uint8 (3,h,w) on `device`.  uint8 input: HWC (PIL / numpy) or CHW; float input: a ToTensor() image (CHW in [0, 1]),
+    converted with round(x * 255), which is exact for such tensors."""
+    gt = _to_array(gt)
+    t = torch.from_numpy(np.ascontiguousarray(gt)) if isinstance(gt, np.ndarray) else gt
+    if t.dim() == 4 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 3:
+        raise ValueError(f"ground truth: expected a 3-dimensional image, got {tuple(t.shape)}")
+    if t.dtype == torch.uint8:
+        hwc = t.shape[-1] == 3 and (t.shape[0] != 3 or isinstance(gt, np.ndarray))
+        t = t.permute(2, 0, 1) if hwc else t
+        if t.shape[0] != 3:
+            raise ValueError(f"ground truth: expected 3 colour channels, got {tuple(t.shape)}")
+        return t.to(device).contiguous()
+    if not t.is_floating_point() or t.shape[0] != 3:
+        raise ValueError(f"ground truth: expected uint8 HWC / CHW or a float CHW ToTensor() image, got {t.dtype} "
+                         f"{tuple(t.shape)}")
+    return torch.round(t.to(device, torch.float32) * 255).clamp_(0, 255).to(torch.uint8).contiguous()
+
+
+def _low_f32(low, device) -> torch.Tensor:
+    """-> fp32 (3,h,w) on `device`: a float CHW tensor as it is, a uint8 HWC image as ToTensor() converts it"""
+    low = _to_array(low)
+    if isinstance(low, np.ndarray):
+        low = torch.from_numpy(np.ascontiguousarray(low))
+        if low.dtype == torch.uint8 and low.dim() == 3 and low.shape[-1] == 3:
+            low = low.permute(2, 0, 1)
+    if low.dim() == 4 and low.shape[0] == 1:
+        low = low[0]
+    if low.dim() != 3 or low.shape[0] != 3:
+        raise ValueError(f"input image: expected (3,h,w), got {tuple(low.shape)}")
+    if low.dtype == torch.uint8:
+        return low.to(device).float().div(255)
+    return low.to(device, torch.float32)
+
+
+# ---- evaluate ---------------------------------------------------------------------------------------------------------
+@dataclass
+class EvalResult:
+    """Means over the evaluated images (in input order, divided by their number) and the per-image values"""
+    alpha: float
+    psnr: float
+    ssim: float
+    psnr_gt_mean: float
+    ssim_gt_mean: float
+    per_image: dict = field(default_factory=dict)     # "psnr" / "ssim" / "psnr_gt_mean" / "ssim_gt_mean" -> list, input order
+    names: list = field(default_factory=list)
+    skipped: list = field(default_factory=list)       # low images without a ground truth (folder_pairs)
+
+
+_KEYS = ("psnr", "ssim", "psnr_gt_mean", "ssim_gt_mean")
+
+
+def _model_device(model):
+    for p in model.parameters():
+        return p.device
+    raise RuntimeError("evaluate: the model has no parameters")
+
+
+@torch.no_grad()
+def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
+             alpha=1.0, batch_size: int = 1, process_group=None):
+    """eval.py + measure.py on the device.  `pairs`: a sequence of (low, gt) -- low a (3,h,w) float image in [0, 1] (or a
+    uint8 HWC image, converted as ToTensor() does), gt uint8 HWC / CHW or a float ToTensor() image of the same size
+    (folder_pairs() yields these).  Each input is reflect-padded to a multiple of 8, run through model(x ** gamma) in eval
+    mode under no_grad with trans.gated / alpha_s / gated2 / alpha set (a tuple result -- CIDNet_TNSM -- gives its [0]),
+    clamped, cropped and quantized to uint8, and measured against its ground truth without and with the GT-mean rescale.
+
+    alpha: a number, or a sequence of numbers (an alpha sweep): the result is then a list with one EvalResult per value, and
+    the model's trunk runs once per batch -- only PHVIT, the quantization and the metrics run per value.
+    batch_size > 1 batches consecutive images of equal padded size.
+    Data-parallel: with torch.distributed initialised (or `process_group` given), rank r evaluates images i % world == r and
+    the per-image values are gathered back into image order with one SUM all-reduce, so every rank returns the same result
+    (with batch_size=1 bit-identical to a single process).
+    The model's attributes and the train / eval mode of every submodule are restored afterwards."""
+    device = _model_device(model)
+    if not device.type == "cuda":
+        raise RuntimeError(_NO_CPU)
+    sweep = isinstance(alpha, (list, tuple))
+    alphas = [float(a) for a in alpha] if sweep else [float(alpha)]
+    if not alphas:
+        raise ValueError("evaluate: empty alpha sweep")
+    n = len(pairs)
+    if n == 0:
+        raise ValueError("evaluate: no image pairs")
+    world, rank = 1, 0
+    if process_group is not None or (dist.is_available() and dist.is_initialized()):
+        world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+    batch_size = max(1, int(batch_size))
+    use_trunk = sweep and hasattr(model, "trunk")
+    trans = model.trans
+    saved_attrs = {k: getattr(trans, k) for k in ("gated", "alpha_s", "gated2", "alpha")}
+    saved_k = {k: trans.__dict__[k] for k in ("_this_k_host", "_this_k_dev") if k in trans.__dict__}
+    saved_modes = [(m, m.training) for m in model.modules()]
+    # rows: images in input order; columns: _KEYS.  This rank fills the rows of its images, zeros elsewhere.
+    res = torch.zeros((len(alphas), n, len(_KEYS)), dtype=torch.float64, device=device)
+    try:
+        model.eval()
+        trans.gated, trans.alpha_s, trans.gated2 = bool(gated), float(alpha_s), bool(gated2)
+        with torch.cuda.device(device):
+            batch = []                                           # [(image index, padded input, gt uint8, (h, w))]
+            for i in range(rank, n, world):
+                low, gt = pairs[i]
+                x = _low_f32(low, device)
+                g = _gt_u8(gt, device)
+                if tuple(g.shape) != tuple(x.shape):
+                    raise ValueError(f"evaluate: image {i}: ground truth {tuple(g.shape[1:])} and input {tuple(x.shape[1:])} "
+                                     "differ in size (resizing the ground truth is not supported)")
+                xp, hw = pad_to_multiple(x.unsqueeze(0), 8)
+                if batch and (len(batch) == batch_size or batch[0][1].shape != xp.shape):
+                    _run_batch(model, batch, gamma, alphas, use_trunk, world, res)
+                    batch = []
+                batch.append((i, xp, g, hw))
+            if batch:
+                _run_batch(model, batch, gamma, alphas, use_trunk, world, res)
+        if world > 1:
+            dist.all_reduce(res, op=dist.ReduceOp.SUM, group=process_group)
+        host = res.cpu().numpy()
+    finally:
+        for k, v in saved_attrs.items():
+            setattr(trans, k, v)
+        trans.__dict__.update(saved_k)
+        for m, mode in saved_modes:
+            m.training = mode
+    names = list(getattr(pairs, "names", range(n)))
+    skipped = list(getattr(pairs, "skipped", []))
+    out = []
+    for ai, a in enumerate(alphas):
+        per = {k: [float(v) for v in host[ai, :, j]] for j, k in enumerate(_KEYS)}
+        means = {}
+        for k, vals in per.items():                               # running sum in input order, / n (measure.py:146-150)
+            acc = 0.0
+            for v in vals:
+                acc += v
+            means[k] = acc / n
+        out.append(EvalResult(alpha=a, per_image=per, names=names, skipped=skipped, **means))
+    return out if sweep else out[0]
+
+
+def _run_batch(model, batch, gamma, alphas, use_trunk, world, res):
+    x = torch.cat([b[1] for b in batch]) if len(batch) > 1 else batch[0][1]
+    xg = x ** gamma
+    trunk = model.trunk(xg) if use_trunk else None
+    first = batch[0][0]
+    for ai, a in enumerate(alphas):
+        model.trans.alpha = a
+        if trunk is not None:
+            out = model.trans.PHVIT_residual(*trunk)
+        else:
+            out = model(xg)
+            if isinstance(out, tuple):                           # CIDNet_TNSM: (rgb, noise map or None)
+                out = out[0]
+        j = 0
+        while j < len(batch):                                    # runs of equal crop size share one launch
+            k = j + 1
+            while k < len(batch) and batch[k][3] == batch[j][3]:
+                k += 1
+            h, w = batch[j][3]
+            q = to_uint8(out[j:k], (h, w))
+            g = torch.stack([b[2] for b in batch[j:k]]) if k - j > 1 else batch[j][2].unsqueeze(0)
+            p0, s0 = psnr_ssim(q, g, gt_mean=False)
+            p1, s1 = psnr_ssim(q, g, gt_mean=True)
+            # this rank's images are every world-th one, so consecutive images of a batch are a strided slice of the rows
+            i0 = first + j * world
+            rows = res[ai, i0:i0 + (k - j - 1) * world + 1:world]
+            for col, v in enumerate((p0, s0, p1, s1)):
+                rows[:, col].copy_(v)
+            j = k
+
+
+# ---- folder pairing (the one piece of host / disk code) ------------------------------------------------------------
+class FolderPairs:
+    """Sequence of (low, gt) pairs read from disk on access: low = the low-light image as ToTensor() gives it (fp32 (3,h,w) in
+    [0, 1]), gt = the ground truth as uint8 (h,w,3); both through PIL's .convert('RGB').  names: the low images' file names;
+    skipped: low images without a ground truth; paths: (low path, gt path) per pair."""
+
+    def __init__(self, paths, names, skipped):
+        self.paths, self.names, self.skipped = paths, names, skipped
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, i):
+        from PIL import Image
+        lp, gp = self.paths[i]
+        with Image.open(lp) as im:
+            low = np.array(im.convert("RGB"))
+        with Image.open(gp) as im:
+            gt = np.array(im.convert("RGB"))
+        return torch.from_numpy(low).permute(2, 0, 1).float().div(255), gt
+
+
+def folder_pairs(low_dir: str, high_dir: str) -> FolderPairs:
+    """Pairs every image file of low_dir (sorted by name) with its ground truth in high_dir, as measure.py:88-131 does: the
+    same file name, else the same stem with .jpg / .JPG / .jpeg / .JPEG / .png / .PNG, in that order.  A low image without
+    one is skipped and reported (a warning and FolderPairs.skipped); unlike measure.py it does not count in any average."""
+    names = sorted(f for f in os.listdir(low_dir)
+                   if os.path.isfile(os.path.join(low_dir, f)) and os.path.splitext(f)[1].lower() in _IMAGE_EXTENSIONS)
+    paths, kept, skipped = [], [], []
+    for name in names:
+        stem = os.path.splitext(name)[0]
+        for cand in (name, *(stem + e for e in GT_EXTENSIONS)):
+            gp = os.path.join(high_dir, cand)
+            if os.path.isfile(gp):
+                paths.append((os.path.join(low_dir, name), gp))
+                kept.append(name)
+                break
+        else:
+            skipped.append(name)
+    if skipped:
+        warnings.warn(f"folder_pairs: no ground truth in {high_dir} for {len(skipped)} image(s): {', '.join(skipped)}")
+    return FolderPairs(paths, kept, skipped)

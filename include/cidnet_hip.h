@@ -9,7 +9,9 @@
  *
  * Conventions
  *   - all tensors are fp32, NCHW-contiguous device memory unless a stride argument says otherwise;
- *     "HW" planes are H*W floats; pointers are plain device pointers owned by the caller;
+ *     "HW" planes are H*W floats; pointers are plain device pointers owned by the caller;  the one
+ *     exception are the evaluation metrics (cidnet_metric_*), whose images are uint8 (B,3,h,w) and
+ *     whose results are fp64 device buffers;
  *   - `stream` is a hipStream_t passed as void* (the caller's current stream; NULL = default);
  *   - functions are stateless and re-entrant, never allocate, never synchronise and never copy to
  *     the host, so a caller may capture them into a hipGraph;  scratch memory comes in through
@@ -26,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 6
+#define CIDNET_ABI_VERSION 7
 
 int cidnet_abi_version(void);
 
@@ -469,6 +471,23 @@ long cidnet_tnsm_noise_loss_ws_floats(void);
 int cidnet_tnsm_noise_loss(const float* noise_map, const float* out_rgb, const float* im, float weight, float* loss,
                            float* g_noise, float* g_out, float* ws, long ws_floats, int B, int C, int H, int W,
                            void* stream);
+
+/* ---- Evaluation metrics (eval.py:40-80 + measure.py:23-150 of the reference): quantize the model output, then PSNR and
+ * SSIM against the ground truth, optionally after the "GT mean" rescale.  Images are uint8 (B,3,h,w) device tensors;
+ * results are one fp64 value per image in caller-owned device buffers (double* -- no host scalar, no synchronisation).
+ * to_uint8: q = (uint8) trunc(clamp(x, 0, 1) * 255.0f) of the top-left h x w crop of x (B,3,Hp,Wp) (eval.py:69-73 with
+ *   ToPILImage's pic.mul(255).byte(); NaN -> 0).
+ * psnr_ssim: psnr[b] = 10 log10(255^2 / (mean((a - g)^2) + 1e-8)) over the 3 h w values (measure.py:66-71; squared errors
+ *   summed exactly); ssim[b] = mean over the three planes of the mean SSIM map on the valid region of the 11 x 11
+ *   Gaussian window (sigma 1.5), C1 = (0.01 255)^2, C2 = (0.03 255)^2, fp64 (measure.py:23-64).  gt_mean != 0: a is first
+ *   replaced by clip(a * s, 0, 255) (fp64; PSNR reads its fp32 cast) with s = mean(gray(g)) / mean(gray(a)) formed on the
+ *   device, gray = (4899 R + 9617 G + 1868 B + 8192) >> 14 (measure.py:138-141).  psnr or ssim may be NULL; with ssim,
+ *   h < 11 or w < 11 is CIDNET_ERR_SHAPE.  Fixed-order reductions: bit-identical results from call to call, and an
+ *   image's values do not depend on the rest of the batch.  ws: cidnet_metric_ws_floats(B, h, w) floats, 8-byte aligned. */
+int cidnet_metric_to_uint8(const float* x, uint8_t* q, int B, int Hp, int Wp, int h, int w, void* stream);
+long cidnet_metric_ws_floats(int B, int h, int w);
+int cidnet_metric_psnr_ssim(const uint8_t* restored, const uint8_t* gt, int gt_mean, double* psnr, double* ssim, float* ws,
+                            long ws_floats, int B, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,91 @@
+"""CPU checks of the evaluation metrics: the fp64 restatement the GPU tests compare against (tests/metrics_ref.py),
+folder_pairs' file pairing, and the refusal of CPU tensors."""
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import metrics_ref as R  # noqa: E402
+
+
+def test_gaussian_window_closed_form():
+    g = R.gaussian_1d()
+    raw = np.array([math.exp(-((i - 5) ** 2) / (2 * 1.5 ** 2)) for i in range(11)])
+    assert np.allclose(g, raw / raw.sum(), rtol=0, atol=1e-16)
+    assert abs(g.sum() - 1.0) < 1e-15 and np.array_equal(g, g[::-1])
+    w = R.gaussian_window()
+    assert w.shape == (11, 11) and abs(w.sum() - 1.0) < 1e-14
+    assert abs(w[5, 5] - g[5] ** 2) < 1e-18
+
+
+def test_separable_filter_equals_the_2d_window():
+    from scipy.signal import correlate2d
+    x = np.random.default_rng(0).integers(0, 256, (23, 31)).astype(np.float64)
+    d = np.abs(R.filter_valid(x) - correlate2d(x, R.gaussian_window(), mode="valid")).max()
+    assert d < 1e-11
+
+
+def test_gray_rule_on_hand_values():
+    px = np.array([[255, 0, 0], [0, 255, 0], [0, 0, 255], [255, 255, 255], [0, 0, 0], [128, 64, 32]], dtype=np.uint8)
+    img = px.T.reshape(3, 1, -1)
+    assert R.gray(img).ravel().tolist() == [76, 150, 29, 255, 0, (4899 * 128 + 9617 * 64 + 1868 * 32 + 8192) >> 14]
+
+
+def test_psnr_of_identical_images():
+    a = np.random.default_rng(1).integers(0, 256, (3, 16, 20), dtype=np.uint8)
+    expect = 10 * math.log10(65025 / 1e-8)
+    assert R.psnr(a, a) == pytest.approx(expect, abs=1e-12)
+    assert R.psnr(a, a, gt_mean=True) == pytest.approx(expect, abs=1e-12)
+    assert abs(R.ssim(a, a) - 1.0) < 1e-14
+
+
+def _png(path, rgb):
+    from PIL import Image
+    Image.fromarray(rgb).save(path)
+
+
+def test_folder_pairs(tmp_path):
+    import hvi_cidnet_amd as P
+    low, high = tmp_path / "low", tmp_path / "high"
+    low.mkdir()
+    high.mkdir()
+    rng = np.random.default_rng(2)
+    imgs = {n: rng.integers(0, 256, (6, 5, 3), dtype=np.uint8) for n in ("b.png", "a.png", "c.bmp", "d.png", "e.png")}
+    for n, im in imgs.items():
+        _png(low / n, im)
+    _png(high / "a.png", imgs["a.png"][::-1].copy())     # same name
+    _png(high / "b.PNG", imgs["b.png"])                  # stem + .PNG, after .png (absent)
+    _png(high / "c.png", imgs["c.bmp"])                  # stem + .jpg wins over stem + .png
+    _png(high / "c.jpg", imgs["c.bmp"])
+    _png(high / "e.JPEG", imgs["e.png"])                 # d has no ground truth
+    (low / "notes.txt").write_text("not an image")
+    with pytest.warns(UserWarning, match="d.png"):
+        pairs = P.folder_pairs(str(low), str(high))
+    assert pairs.names == ["a.png", "b.png", "c.bmp", "e.png"]
+    assert pairs.skipped == ["d.png"]
+    assert len(pairs) == 4
+    assert [os.path.basename(g) for _, g in pairs.paths] == ["a.png", "b.PNG", "c.jpg", "e.JPEG"]
+    lo, gt = pairs[0]
+    assert lo.dtype == torch.float32 and tuple(lo.shape) == (3, 6, 5)
+    assert torch.equal(lo, torch.from_numpy(imgs["a.png"]).permute(2, 0, 1).float().div(255))
+    assert gt.dtype == np.uint8 and np.array_equal(gt, imgs["a.png"][::-1])
+
+
+def test_metrics_refuse_cpu_tensors():
+    import hvi_cidnet_amd as P
+    from hvi_cidnet_amd import metrics as M
+    q = torch.zeros(1, 3, 16, 16, dtype=torch.uint8)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        M.to_uint8(torch.rand(1, 3, 16, 16))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        M.psnr(q, q)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        M.ssim(q, q, gt_mean=True)
+    m = P.CIDNet(channels=[12, 12, 24, 48])
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        P.evaluate(m, [(torch.rand(3, 16, 16), np.zeros((16, 16, 3), np.uint8))])
+    assert m.training                                    # nothing was touched

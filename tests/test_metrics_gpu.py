@@ -1,0 +1,119 @@
+"""GPU: the metric kernels (csrc/metrics.hip through hvi_cidnet_amd.metrics) against the fp64 restatement of
+tests/metrics_ref.py -- quantization bit for bit, PSNR within 1e-6 dB, SSIM within 1e-10, with and without the GT-mean
+rescale -- and their reproducibility (bit-identical repeated calls, an image's values independent of its batch)."""
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import metrics_ref as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+PSNR_TOL, SSIM_TOL = 1e-6, 1e-10
+
+
+def _pair(rng, shape, kind="noisy"):
+    """(restored, gt) uint8 (3,h,w) with realistic structure: a smooth gradient scene plus texture, the restored image a
+    darker / brighter noisy copy (so the GT-mean scale is not 1)"""
+    _, h, w = shape
+    yy, xx = np.meshgrid(np.linspace(0, 1, h), np.linspace(0, 1, w), indexing="ij")
+    base = np.stack([120 + 90 * np.sin(5 * xx + c) * yy for c in range(3)]) + rng.normal(0, 25, shape)
+    gt = np.clip(base, 0, 255).astype(np.uint8)
+    if kind == "random":
+        return rng.integers(0, 256, shape, dtype=np.uint8), gt
+    gain = {"noisy": 0.8, "dark": 0.3, "bright": 1.6}[kind]
+    restored = np.clip(gt.astype(np.float64) * gain + rng.normal(0, 12, shape), 0, 255).astype(np.uint8)
+    return restored, gt
+
+
+def _check(rs, gs, dev):
+    a = torch.from_numpy(np.stack(rs)).to(dev)
+    g = torch.from_numpy(np.stack(gs)).to(dev)
+    for gm in (False, True):
+        p, s = (t.cpu().numpy() for t in P_M().psnr_ssim(a, g, gt_mean=gm))
+        p1, s1 = P_M().psnr(a, g, gt_mean=gm).cpu().numpy(), P_M().ssim(a, g, gt_mean=gm).cpu().numpy()
+        assert np.array_equal(p, p1) and np.array_equal(s, s1)        # one-metric calls: the same values
+        for i, (r_, g_) in enumerate(zip(rs, gs)):
+            rp, rs_ = R.psnr(r_, g_, gt_mean=gm), R.ssim(r_, g_, gt_mean=gm)
+            assert abs(p[i] - rp) <= PSNR_TOL, (i, gm, p[i], rp)
+            assert abs(s[i] - rs_) <= SSIM_TOL, (i, gm, s[i], rs_)
+
+
+def P_M():
+    from hvi_cidnet_amd import metrics
+    return metrics
+
+
+def test_to_uint8_bit_equal_to_torch(dev):
+    g = torch.Generator().manual_seed(3)
+    x = torch.rand(2, 3, 24, 40, generator=g) * 1.4 - 0.2                 # negatives and values above 1
+    k = torch.arange(256, dtype=torch.float32) / 255                        # right at the k/255 boundaries ...
+    edge = torch.cat([k, torch.nextafter(k, torch.full_like(k, 2.0)), torch.nextafter(k, torch.full_like(k, -1.0)),
+                      torch.tensor([0.0, -0.0, 1.0, -1e-30, 1e-30, 1.0000001, 3.0, -5.0])])
+    flat = x.view(-1)
+    flat[:edge.numel()] = edge
+    flat[-edge.numel():] = edge.flip(0)
+    ref = torch.clamp(x, 0, 1).mul(255).byte()
+    M = P_M()
+    q = M.to_uint8(x.to(dev))
+    assert q.dtype == torch.uint8 and torch.equal(q.cpu(), ref)
+    qc = M.to_uint8(x.to(dev), size=(19, 33))                              # padded -> cropped
+    assert tuple(qc.shape) == (2, 3, 19, 33) and torch.equal(qc.cpu(), ref[:, :, :19, :33])
+    q3 = M.to_uint8(x[1].to(dev), size=(7, 40))
+    assert torch.equal(q3.cpu(), ref[1, :, :7])
+
+
+@pytest.mark.parametrize("shape", [(3, 11, 11), (3, 37, 51), (3, 400, 600), (3, 1024, 1024)])
+def test_psnr_ssim_match_the_restatement(dev, shape):
+    rng = np.random.default_rng(shape[1] * 7 + shape[2])
+    r, g = _pair(rng, shape)
+    _check([r], [g], dev)
+
+
+def test_mixed_batch_matches_the_restatement(dev):
+    rng = np.random.default_rng(11)
+    pairs = [_pair(rng, (3, 48, 70), kind) for kind in ("dark", "bright", "random")]
+    _check([p[0] for p in pairs], [p[1] for p in pairs], dev)
+
+
+def test_identical_images(dev):
+    M = P_M()
+    rng = np.random.default_rng(12)
+    a = torch.from_numpy(np.stack([_pair(rng, (3, 40, 56))[1] for _ in range(2)])).to(dev)
+    for gm in (False, True):
+        p, s = M.psnr_ssim(a, a.clone(), gt_mean=gm)
+        assert torch.equal(s.cpu(), torch.ones(2, dtype=torch.float64))
+        assert np.allclose(p.cpu().numpy(), 10 * math.log10(65025 / 1e-8), rtol=0, atol=1e-9)
+
+
+def test_reproducible_and_batch_independent(dev):
+    M = P_M()
+    rng = np.random.default_rng(13)
+    pairs = [_pair(rng, (3, 96, 136), kind) for kind in ("noisy", "dark", "random", "bright")]
+    a = torch.from_numpy(np.stack([p[0] for p in pairs])).to(dev)
+    g = torch.from_numpy(np.stack([p[1] for p in pairs])).to(dev)
+    for gm in (False, True):
+        first = [t.clone() for t in M.psnr_ssim(a, g, gt_mean=gm)]
+        again = M.psnr_ssim(a, g, gt_mean=gm)
+        assert all(torch.equal(x, y) for x, y in zip(first, again))
+        for i in range(4):
+            alone = M.psnr_ssim(a[i:i + 1], g[i:i + 1], gt_mean=gm)
+            assert torch.equal(alone[0], first[0][i:i + 1]) and torch.equal(alone[1], first[1][i:i + 1])
+        sub = M.psnr_ssim(a[1:3], g[1:3], gt_mean=gm)
+        assert torch.equal(sub[0], first[0][1:3]) and torch.equal(sub[1], first[1][1:3])
+
+
+def test_shape_checks(dev):
+    M = P_M()
+    a = torch.zeros(1, 3, 10, 40, dtype=torch.uint8, device=dev)
+    with pytest.raises(RuntimeError, match="11 x 11"):
+        M.ssim(a, a)
+    assert M.psnr(a, a).shape == (1,)                                      # PSNR alone has no minimum size
+    with pytest.raises(RuntimeError, match="uint8"):
+        M.psnr(a.float(), a.float())
+    with pytest.raises(RuntimeError, match="differ"):
+        M.psnr(a, a[:, :, :, :20])
