@@ -8,7 +8,15 @@ SSIM, optionally after the "GT mean" rescale) without the PNG round trip through
     res = M.evaluate(model, pairs, gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0, batch_size=1)
     pairs = M.folder_pairs(low_dir, high_dir)
 
-The kernels are csrc/metrics.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
+and, for the sets without ground truth (eval.py --unpaired + measure_niqe_bris.py), NIQE:
+
+    prm = M.load_niqe_params(path)          # the reference's loss/niqe_pris_params.npz (not shipped: pass its path)
+    f = M.niqe_features(q, prm)             # uint8 (B,3,h,w) -> (B, blocks, 36) float64 on the device
+    s = M.niqe(q, prm)                      # (B,) float64 (the 36 x 36 tail runs on the host: one copy per batch)
+    res = M.evaluate_unpaired(model, images, prm, alpha=1.0, gamma=1.0, batch_size=1)
+    images = M.folder_images(dir)
+
+The kernels are csrc/metrics.hip and csrc/niqe.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
 Differences from the reference scripts, none of which changes a per-image value:
   * measure.py counts a low image without a ground truth in the divisor of its averages (it skips the image after
     `n += 1`); here such an image is skipped and reported (FolderPairs.skipped, EvalResult.skipped) and not counted;
@@ -16,10 +24,15 @@ Differences from the reference scripts, none of which changes a per-image value:
     attribute it touches and the train / eval mode of every submodule;
   * a ground truth whose size differs from the output raises (measure.py:134 would bicubic-resize the output);
   * PSNR sums its squared errors exactly (fp64) where measure.py averages in fp32: < 1e-4 dB apart;
-  * LPIPS is not computed (it needs AlexNet weights and the lpips package's heads).
+  * LPIPS is not computed (it needs AlexNet weights and the lpips package's heads);
+  * NIQE: the half-size image sums its 8 taps in fp64 and rounds once per pass where the reference sums them in fp32 (two
+    fp32 ulps apart at most), and the block moments are summed in fp64 where the reference's are fp32 means; an image with
+    fewer than two NaN-free blocks scores NaN (the reference raises from inside the SVD); BRISQUE and the JPEG round trip
+    that eval.py's output files go through for .jpg inputs are not reproduced.
 """
 from __future__ import annotations
 
+import math
 import os
 import warnings
 from dataclasses import dataclass, field
@@ -329,3 +342,357 @@ def folder_pairs(low_dir: str, high_dir: str) -> FolderPairs:
     if skipped:
         warnings.warn(f"folder_pairs: no ground truth in {high_dir} for {len(skipped)} image(s): {', '.join(skipped)}")
     return FolderPairs(paths, kept, skipped)
+
+
+# ---- NIQE (measure_niqe_bris.py -> loss/niqe_utils.py) -----------------------------------------------------------------
+NIQE_BLOCK = 96
+# data/util.py: is_image_file -- a case-sensitive suffix test
+UNPAIRED_EXTENSIONS = (".png", ".jpg", ".bmp", ".JPG", ".jpeg")
+_NIQE_NO_PARAMS = ("NIQE needs the pristine-model parameters (mu_pris_param, cov_pris_param, gaussian_window): pass a NiqeParams "
+                   "or the path of the reference's loss/niqe_pris_params.npz (load_niqe_params); they are data of the reference "
+                   "and are not shipped with this package")
+
+
+@dataclass
+class NiqeParams:
+    """The pristine multivariate-Gaussian model and the MSCN window of the reference's niqe_pris_params.npz"""
+    mu_pris_param: np.ndarray                           # (1, 36) fp64
+    cov_pris_param: np.ndarray                          # (36, 36) fp64
+    gaussian_window: np.ndarray                         # (7, 7) fp64
+    _dev: dict = field(default_factory=dict, repr=False, compare=False)      # device index -> the window as a device tensor
+
+    def window_on(self, device):
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(np.ascontiguousarray(self.gaussian_window, dtype=np.float64).ravel()).to(device)
+        return self._dev[key]
+
+
+def load_niqe_params(path) -> NiqeParams:
+    """Reads mu_pris_param (1,36), cov_pris_param (36,36) and gaussian_window (7,7) from an .npz with the reference's keys"""
+    if path is None:
+        raise ValueError(_NIQE_NO_PARAMS)
+    with np.load(path) as z:
+        missing = [k for k in ("mu_pris_param", "cov_pris_param", "gaussian_window") if k not in z.files]
+        if missing:
+            raise ValueError(f"load_niqe_params: {path} lacks {', '.join(missing)}")
+        mu, cov, win = (np.array(z[k], dtype=np.float64) for k in ("mu_pris_param", "cov_pris_param", "gaussian_window"))
+    if mu.size != 36 or cov.shape != (36, 36) or win.shape != (7, 7):
+        raise ValueError(f"load_niqe_params: unexpected shapes {mu.shape}, {cov.shape}, {win.shape} in {path}")
+    if not np.array_equal(win, win[::-1, ::-1]):
+        raise ValueError("load_niqe_params: the window is not point-symmetric (the kernels correlate, the reference convolves)")
+    return NiqeParams(mu.reshape(1, 36), cov, win)
+
+
+def _niqe_params(params) -> NiqeParams:
+    if isinstance(params, NiqeParams):
+        return params
+    if params is None:
+        raise ValueError(_NIQE_NO_PARAMS)
+    return load_niqe_params(params)
+
+
+NIQE_GRID = 9801
+_niqe_tables_host = None
+_niqe_tables_dev = {}
+
+
+def niqe_tables() -> np.ndarray:
+    """(4, 9801) fp64 over alpha = np.arange(0.2, 10.001, 0.001): r_gam = gamma(2/a)^2 / (gamma(1/a) gamma(3/a)),
+    sqrt(gamma(1/a) / gamma(3/a)), gamma(2/a) / gamma(1/a), alpha -- what estimate_aggd_param / compute_feature evaluate with
+    scipy's gamma, here with math.gamma (2.2e-15 relative apart)"""
+    global _niqe_tables_host
+    if _niqe_tables_host is None:
+        a = np.arange(0.2, 10.001, 0.001)
+        assert a.size == NIQE_GRID
+        rec = 1.0 / a
+        g1 = np.array([math.gamma(v) for v in rec])
+        g2 = np.array([math.gamma(v) for v in rec * 2])
+        g3 = np.array([math.gamma(v) for v in rec * 3])
+        b13 = np.sqrt(np.array([math.gamma(1 / v) / math.gamma(3 / v) for v in a]))
+        m21 = np.array([math.gamma(2 / v) / math.gamma(1 / v) for v in a])
+        _niqe_tables_host = np.ascontiguousarray(np.stack([g2 * g2 / (g1 * g3), b13, m21, a]))
+    return _niqe_tables_host
+
+
+def _niqe_tables_on(device):
+    """uploaded once per process and device"""
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if key not in _niqe_tables_dev:
+        _niqe_tables_dev[key] = torch.from_numpy(niqe_tables()).to(device)
+    return _niqe_tables_dev[key]
+
+
+def _niqe_input(images, what):
+    _on_device(images)
+    if images.dtype != torch.uint8:
+        raise RuntimeError(f"{what} takes uint8 images (got {images.dtype}); see to_uint8")
+    x = _batched(images, what)
+    h, w = x.shape[-2:]
+    if h < NIQE_BLOCK or w < NIQE_BLOCK:
+        raise ValueError(f"{what}: images of at least {NIQE_BLOCK} x {NIQE_BLOCK} pixels are needed (got {h} x {w}): NIQE is "
+                         "measured on whole 96 x 96 blocks")
+    return x
+
+
+def niqe_luma(images: torch.Tensor, crop: bool = True) -> torch.Tensor:
+    """uint8 (B,3,h,w) -> uint8 (B,hc,wc): the Y plane the reference's NIQE works on (to_y_channel on an RGB array: the
+    BT.601 weights in B, G, R order, rounded half to even), cropped to whole blocks (crop=False: the whole image).  A stage
+    of niqe_features, for tests."""
+    x = _niqe_input(images, "niqe_luma")
+    B, _, h, w = x.shape
+    hc, wc = (h // NIQE_BLOCK * NIQE_BLOCK, w // NIQE_BLOCK * NIQE_BLOCK) if crop else (h, w)
+    y = torch.empty((B, hc, wc), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        lib().call("cidnet_metric_niqe_luma", ops._p(x), ops._p(y), B, h, w, hc, wc, ops._stream())
+    return y
+
+
+def _plane(img, what):
+    _on_device(img)
+    if img.dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError(f"{what}: expected a uint8 or fp32 plane (got {img.dtype})")
+    if img.dim() == 2:
+        img = img.unsqueeze(0)
+    if img.dim() != 3:
+        raise RuntimeError(f"{what}: expected (B,h,w) or (h,w), got {tuple(img.shape)}")
+    return img.contiguous()
+
+
+def niqe_half(img: torch.Tensor) -> torch.Tensor:
+    """(B,h,w) uint8 or fp32 plane in 0..255, h and w even -> fp32 (B,h/2,w/2): imresize(img / 255, 0.5) * 255 (MATLAB-style
+    antialiased bicubic).  A stage of niqe_features, for tests."""
+    x = _plane(img, "niqe_half")
+    B, h, w = x.shape
+    if h % 2 or w % 2 or h < 4 or w < 4:
+        raise ValueError(f"niqe_half: even sizes of at least 4 are needed (got {h} x {w})")
+    rows = torch.empty((B, h // 2, w), dtype=torch.float32, device=x.device)
+    out = torch.empty((B, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        lib().call("cidnet_metric_niqe_half", ops._p(x), int(x.dtype == torch.float32), ops._p(rows), ops._p(out), B, h, w,
+                   ops._stream())
+    return out
+
+
+def niqe_mscn(img: torch.Tensor, params, block: int = NIQE_BLOCK):
+    """(B,h,w) uint8 or fp32 plane (h, w multiples of block = 96 or 48) -> (mscn fp32 (B,h,w), moments fp64 (B,blocks,5,6)):
+    the locally normalised image and, per block and per map (the block; the block times itself rolled by (0,1), (1,0), (1,1),
+    (1,-1)), the six sums of the asymmetric-Gaussian fit.  A stage of niqe_features, for tests."""
+    prm = _niqe_params(params)
+    x = _plane(img, "niqe_mscn")
+    B, h, w = x.shape
+    if block not in (96, 48) or h % block or w % block or h == 0 or w == 0:
+        raise ValueError(f"niqe_mscn: block {block} (96 or 48) must divide the {h} x {w} plane")
+    nblk = (h // block) * (w // block)
+    m = torch.empty((B, h, w), dtype=torch.float32, device=x.device)
+    mom = torch.empty((B, nblk, 5, 6), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        lib().call("cidnet_metric_niqe_moments", ops._p(x), int(x.dtype == torch.float32), ops._p(prm.window_on(x.device)), block,
+                   ops._p(m), ops._p(mom), B, h, w, ops._stream())
+    return m, mom
+
+
+def niqe_fit(moments: torch.Tensor, block: int = NIQE_BLOCK) -> torch.Tensor:
+    """moments fp64 (..., 5, 6) of blocks of block x block pixels -> the 18 features (..., 18) fp64.  A stage of
+    niqe_features, for tests."""
+    _on_device(moments)
+    if moments.dtype != torch.float64 or moments.dim() < 2 or tuple(moments.shape[-2:]) != (5, 6):
+        raise RuntimeError(f"niqe_fit: expected fp64 (...,5,6) moments, got {moments.dtype} {tuple(moments.shape)}")
+    mom = moments.contiguous()
+    n = mom.numel() // 30
+    feat = torch.empty(tuple(mom.shape[:-2]) + (18,), dtype=torch.float64, device=mom.device)
+    with torch.cuda.device(mom.device):
+        lib().call("cidnet_metric_niqe_fit", ops._p(mom), ops._p(_niqe_tables_on(mom.device)), int(block), ops._p(feat), 18, n,
+                   ops._stream())
+    return feat
+
+
+def niqe_features(images: torch.Tensor, params) -> torch.Tensor:
+    """uint8 (B,3,h,w) (or (3,h,w)) on the device -> (B, blocks, 36) float64 on the device: per 96 x 96 block of the
+    top-left (h // 96 * 96, w // 96 * 96) crop, in the reference's block order (for w: for h), the 18 features at full size
+    and the 18 at half size (niqe_utils.py: niqe()).  A row holds NaN where a fit has an empty tail or no variance.
+    params: a NiqeParams or the path of the reference's niqe_pris_params.npz."""
+    prm = _niqe_params(params)
+    x = _niqe_input(images, "niqe_features")
+    B, _, h, w = x.shape
+    nblk = (h // NIQE_BLOCK) * (w // NIQE_BLOCK)
+    n = lib().raw("cidnet_metric_niqe_ws_floats")(B, h, w)
+    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+    feat = torch.empty((B, nblk, 36), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        lib().call("cidnet_metric_niqe_features", ops._p(x), ops._p(prm.window_on(x.device)), ops._p(_niqe_tables_on(x.device)),
+                   ops._p(feat), ops._p(ws), n, B, h, w, ops._stream())
+    return feat
+
+
+def niqe_score(features, params) -> np.ndarray:
+    """(B, blocks, 36) features (a device or host tensor, or an array) -> (B,) fp64 numpy: nanmean over the blocks, covariance
+    of the NaN-free rows, sqrt(d pinv((cov_pris + cov) / 2) d^T) (niqe_utils.py: the tail of niqe()), in numpy fp64 on the
+    host.  Fewer than two NaN-free blocks: NaN (the reference raises from inside the SVD there)."""
+    prm = _niqe_params(params)
+    f = features.detach().cpu().numpy() if isinstance(features, torch.Tensor) else np.asarray(features, dtype=np.float64)
+    if f.ndim == 2:
+        f = f[None]
+    out = np.full(f.shape[0], np.nan)
+    for b, fb in enumerate(f):
+        ok = ~np.isnan(fb).any(axis=1)
+        if ok.sum() < 2:
+            continue
+        with np.errstate(all="ignore"):
+            mu = np.nanmean(fb, axis=0)
+        cov = np.cov(fb[ok], rowvar=False)
+        d = prm.mu_pris_param - mu
+        out[b] = np.sqrt((d @ np.linalg.pinv((prm.cov_pris_param + cov) / 2) @ d.T).item())
+    return out
+
+
+def niqe(images: torch.Tensor, params) -> torch.Tensor:
+    """uint8 (B,3,h,w) (or (3,h,w)) on the device -> (B,) float64 on the device: calculate_niqe(image) of the reference with
+    its defaults (Y of the RGB array as the reference forms it, no border crop).  The features come from the device
+    kernels; the 36 x 36 tail runs on the host after one device-to-host copy of the batch's features."""
+    feat = niqe_features(images, params)
+    return torch.from_numpy(niqe_score(feat, params)).to(feat.device)
+
+
+@dataclass
+class UnpairedResult:
+    """Mean NIQE over the evaluated images (running sum in input order, divided by their number) and the per-image values"""
+    alpha: float
+    niqe: float
+    per_image: dict = field(default_factory=dict)     # "niqe" -> list, input order
+    names: list = field(default_factory=list)
+
+
+@torch.no_grad()
+def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batch_size: int = 1, process_group=None):
+    """eval.py --unpaired + measure_niqe_bris.py on the device.  `images`: a sequence of (3,h,w) float images in [0, 1] (or
+    uint8 HWC images, converted as ToTensor() does; folder_images() yields these), each at least 96 x 96.  Each is reflect-
+    padded to a multiple of 8, run through model(x ** gamma) in eval mode under no_grad with trans.gated2 = True and
+    trans.alpha = alpha (a tuple result -- CIDNet_TNSM -- gives its [0]), clamped, cropped, quantized to uint8 and scored
+    with NIQE.  params: a NiqeParams or the path of the reference's niqe_pris_params.npz.
+
+    alpha: a number, or a sequence (a sweep): the result is then a list with one UnpairedResult per value and the model's
+    trunk runs once per batch, as in evaluate().  batch_size > 1 batches consecutive images of equal padded size.
+    Data-parallel as evaluate(): rank r scores images i % world == r, one SUM all-reduce gathers the values.
+    The model's attributes and the train / eval mode of every submodule are restored afterwards.
+    Not reproduced: the JPEG round trip of eval.py's outputs for .jpg inputs, and BRISQUE."""
+    prm = _niqe_params(params)
+    device = _model_device(model)
+    if not device.type == "cuda":
+        raise RuntimeError(_NO_CPU)
+    sweep = isinstance(alpha, (list, tuple))
+    alphas = [float(a) for a in alpha] if sweep else [float(alpha)]
+    if not alphas:
+        raise ValueError("evaluate_unpaired: empty alpha sweep")
+    n = len(images)
+    if n == 0:
+        raise ValueError("evaluate_unpaired: no images")
+    world, rank = 1, 0
+    if process_group is not None or (dist.is_available() and dist.is_initialized()):
+        world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+    batch_size = max(1, int(batch_size))
+    use_trunk = sweep and hasattr(model, "trunk")
+    trans = model.trans
+    saved_attrs = {k: getattr(trans, k) for k in ("gated", "alpha_s", "gated2", "alpha")}
+    saved_k = {k: trans.__dict__[k] for k in ("_this_k_host", "_this_k_dev") if k in trans.__dict__}
+    saved_modes = [(m, m.training) for m in model.modules()]
+    res = torch.zeros((len(alphas), n), dtype=torch.float64, device=device)      # this rank fills its images, zeros elsewhere
+    try:
+        model.eval()
+        trans.gated2 = True
+        with torch.cuda.device(device):
+            batch = []                                           # [(image index, padded input, (h, w))]
+            for i in range(rank, n, world):
+                x = _image_f32(images[i], device)
+                if x.shape[1] < NIQE_BLOCK or x.shape[2] < NIQE_BLOCK:
+                    raise ValueError(f"evaluate_unpaired: image {i} is {x.shape[1]} x {x.shape[2]}; NIQE needs at least "
+                                     f"{NIQE_BLOCK} x {NIQE_BLOCK} pixels")
+                xp, hw = pad_to_multiple(x.unsqueeze(0), 8)
+                if batch and (len(batch) == batch_size or batch[0][1].shape != xp.shape):
+                    _run_unpaired_batch(model, batch, gamma, alphas, use_trunk, world, res, prm)
+                    batch = []
+                batch.append((i, xp, hw))
+            if batch:
+                _run_unpaired_batch(model, batch, gamma, alphas, use_trunk, world, res, prm)
+        if world > 1:
+            dist.all_reduce(res, op=dist.ReduceOp.SUM, group=process_group)
+        host = res.cpu().numpy()
+    finally:
+        for k, v in saved_attrs.items():
+            setattr(trans, k, v)
+        trans.__dict__.update(saved_k)
+        for m, mode in saved_modes:
+            m.training = mode
+    names = list(getattr(images, "names", range(n)))
+    out = []
+    for ai, a in enumerate(alphas):
+        vals = [float(v) for v in host[ai]]
+        acc = 0.0
+        for v in vals:                                            # running sum in input order, / n (measure_niqe_bris.py)
+            acc += v
+        out.append(UnpairedResult(alpha=a, niqe=acc / n, per_image={"niqe": vals}, names=names))
+    return out if sweep else out[0]
+
+
+def _image_f32(img, device) -> torch.Tensor:
+    """-> fp32 (3,h,w) on `device`.  A uint8 image (HWC array / PIL image, or a CHW tensor) becomes ToTensor()'s x / 255 by a
+    true division (dividing by a host scalar on the device would multiply by fl(1/255): one ulp off for some levels, which
+    `x ** gamma` carries into the output); anything else goes through _low_f32."""
+    a = _to_array(img)
+    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+    if t.dtype != torch.uint8:
+        return _low_f32(a, device)
+    if t.dim() == 3 and t.shape[-1] == 3 and (t.shape[0] != 3 or isinstance(a, np.ndarray)):
+        t = t.permute(2, 0, 1)
+    if t.dim() != 3 or t.shape[0] != 3:
+        raise ValueError(f"input image: expected (3,h,w) or (h,w,3), got {tuple(t.shape)}")
+    return t.to(device).float() / torch.full((), 255.0, dtype=torch.float32, device=device)
+
+
+def _run_unpaired_batch(model, batch, gamma, alphas, use_trunk, world, res, prm):
+    x = torch.cat([b[1] for b in batch]) if len(batch) > 1 else batch[0][1]
+    xg = x ** gamma
+    trunk = model.trunk(xg) if use_trunk else None
+    first = batch[0][0]
+    for ai, a in enumerate(alphas):
+        model.trans.alpha = a
+        if trunk is not None:
+            out = model.trans.PHVIT_residual(*trunk)
+        else:
+            out = model(xg)
+            if isinstance(out, tuple):                           # CIDNet_TNSM: (rgb, noise map or None)
+                out = out[0]
+        j = 0
+        while j < len(batch):                                    # runs of equal crop size share one launch
+            k = j + 1
+            while k < len(batch) and batch[k][2] == batch[j][2]:
+                k += 1
+            q = to_uint8(out[j:k], batch[j][2])
+            i0 = first + j * world
+            res[ai, i0:i0 + (k - j - 1) * world + 1:world].copy_(niqe(q, prm))
+            j = k
+
+
+class FolderImages:
+    """Sequence of images read from disk on access, each as ToTensor() gives it (fp32 (3,h,w) in [0, 1]) through PIL's
+    .convert('RGB').  names: the file names; paths: their paths."""
+
+    def __init__(self, paths, names):
+        self.paths, self.names = paths, names
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, i):
+        from PIL import Image
+        with Image.open(self.paths[i]) as im:
+            a = np.array(im.convert("RGB"))
+        return torch.from_numpy(a).permute(2, 0, 1).float().div(255)
+
+
+def folder_images(directory: str) -> FolderImages:
+    """Every image file of `directory`, sorted by path, chosen as the reference's unpaired loader chooses them (data/util.py:
+    is_image_file: the name ends in .png, .jpg, .bmp, .JPG or .jpeg, case-sensitively); loaded lazily."""
+    names = sorted(f for f in os.listdir(directory)
+                   if f.endswith(UNPAIRED_EXTENSIONS) and os.path.isfile(os.path.join(directory, f)))
+    return FolderImages([os.path.join(directory, f) for f in names], names)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 7
+#define CIDNET_ABI_VERSION 8
 
 int cidnet_abi_version(void);
 
@@ -488,6 +488,42 @@ int cidnet_metric_to_uint8(const float* x, uint8_t* q, int B, int Hp, int Wp, in
 long cidnet_metric_ws_floats(int B, int h, int w);
 int cidnet_metric_psnr_ssim(const uint8_t* restored, const uint8_t* gt, int gt_mean, double* psnr, double* ssim, float* ws,
                             long ws_floats, int B, int h, int w, void* stream);
+
+/* ---- NIQE features (measure_niqe_bris.py -> loss/niqe_utils.py: calculate_niqe with its defaults): the no-reference
+ * score of the unpaired sets, per image up to its (blocks, 36) feature matrix; the 36 x 36 tail (nanmean, covariance,
+ * pinv) is the caller's, on the host.  Images are uint8 (B,3,h,w), h, w >= 96; hc = h / 96 * 96, wc = w / 96 * 96; blocks
+ * are 96 x 96 (48 x 48 at the half-size scale), counted in column-major order (for w: for h), blocks = (hc / 96)(wc / 96).
+ * window: the 7 x 7 `gaussian_window` of niqe_pris_params.npz, 49 fp64 values on the device.  tables: 4 x 9801 fp64 values
+ * on the device over alpha[k] = np.arange(0.2, 10.001, 0.001)[k] (estimate_aggd_param): r_gam = gamma(2/a)^2 / (gamma(1/a)
+ * gamma(3/a)) | sqrt(gamma(1/a) / gamma(3/a)) | gamma(2/a) / gamma(1/a) | alpha.  Every rounding of the reference is kept:
+ * luma: y = (uint8) rint(fp32(fp32((24.966 R' + 128.553 G' + 65.481 B' + 16) / 255) * 255.0f)), R' = fp32(R) / 255.0f, the dot
+ *   product in fp64, of the top-left hc x wc crop -- the reference passes RGB to a BGR routine (to_y_channel, bgr2ycbcr),
+ *   and that effective rule is the contract.
+ * half: out (B,h/2,w/2) = the antialiased bicubic imresize(img / 255, 0.5) * 255 of img (B,h,w; uint8, or fp32 when img_f32
+ *   != 0; h, w even): taps [-3 -9 29 111 111 29 -9 -3] / 256 on inputs 2k-3 .. 2k+4, symmetric reflection, output rows
+ *   first (into `rows`, (B,h/2,w) floats of scratch), then columns, fp64 sums rounded to fp32 once per pass (the reference
+ *   sums the taps in fp32: up to 2 fp32 ulps apart).
+ * moments: per block of img (B,h,w; uint8 or fp32; h, w multiples of block = 96 or 48) the MSCN values (img - mu) /
+ *   (sigma + 1), mu = fp32(G * img), sigma = sqrt(|fp32(G * fp32(img^2)) - mu^2|) in fp32, the window sums in fp64 with a
+ *   replicated border (niqe(): scipy's convolve on fp32 arrays), and from them moments (B,blocks,5,6) fp64: for the block
+ *   and for the block times itself rolled inside the block by (0,1), (1,0), (1,1), (1,-1) (compute_feature; the product
+ *   rounded to fp32) the count and sum of squares of the negatives, the same of the positives, sum |v| and sum v^2.
+ *   mscn (optional, (B,h,w) fp32) receives the map; without it the map never leaves the compute unit.
+ * fit: for each of n_blocks blocks (5 fits, 6 sums each) the 18 features of compute_feature at feat + block * feat_stride:
+ *   alpha, (beta_l + beta_r) / 2, then per rolled map alpha, mean, beta_l, beta_r; alpha is the FIRST minimum of
+ *   (r_gam - rhatnorm)^2, entry 0 when rhatnorm is NaN (numpy's argmin), and NaN propagates into the betas as in numpy.
+ * features: all of the above for rgb (B,3,h,w): feat (B,blocks,36) fp64 = scale-1 features | half-size-scale features.
+ *   ws: cidnet_metric_niqe_ws_floats(B, h, w) floats, 8-byte aligned.  h < 96 or w < 96 is CIDNET_ERR_SHAPE.
+ * Fixed-order reductions: bit-identical results from call to call, independent of the rest of the batch. */
+int cidnet_metric_niqe_luma(const uint8_t* rgb, uint8_t* y, int B, int h, int w, int hc, int wc, void* stream);
+int cidnet_metric_niqe_half(const void* img, int img_f32, float* rows, float* out, int B, int h, int w, void* stream);
+int cidnet_metric_niqe_moments(const void* img, int img_f32, const double* window, int block, float* mscn, double* moments,
+                               int B, int h, int w, void* stream);
+int cidnet_metric_niqe_fit(const double* moments, const double* tables, int block, double* feat, int feat_stride,
+                           long n_blocks, void* stream);
+long cidnet_metric_niqe_ws_floats(int B, int h, int w);
+int cidnet_metric_niqe_features(const uint8_t* rgb, const double* window, const double* tables, double* feat, float* ws,
+                                long ws_floats, int B, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }
