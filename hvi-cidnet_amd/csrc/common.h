@@ -98,6 +98,12 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // Sum over the block; result valid in thread 0.  `red` = LDS scratch of >= blockDim/64 floats.
 __device__ __forceinline__ float block_sum(float v, float* red) {
   v = wave_sum(v);

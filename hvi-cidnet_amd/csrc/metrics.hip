@@ -51,12 +51,6 @@ __device__ __forceinline__ unsigned gray601(unsigned r, unsigned g, unsigned b) 
   return (4899u * r + 9617u * g + 1868u * b + 8192u) >> 14;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void to_uint8_kernel(const float* __restrict__ x, uint8_t* __restrict__ q, long total, int Hp,
                                                       int Wp, int h, int w) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;

@@ -32,12 +32,6 @@ constexpr int kThreads = 256;
 constexpr int kGrid = 9801;                                     // alpha = 0.2, 0.201, ..., 10.0
 constexpr int kMaps = 5, kSums = 6;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void niqe_luma_kernel(const uint8_t* __restrict__ rgb, uint8_t* __restrict__ y, long total,
                                                        int h, int w, int hc, int wc) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;

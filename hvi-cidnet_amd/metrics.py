@@ -150,20 +150,21 @@ def _gt_u8(gt, device) -> torch.Tensor:
     return torch.round(t.to(device, torch.float32) * 255).clamp_(0, 255).to(torch.uint8).contiguous()
 
 
-def _low_f32(low, device) -> torch.Tensor:
-    """-> fp32 (3,h,w) on `device`: a float CHW tensor as it is, a uint8 HWC image as ToTensor() converts it"""
-    low = _to_array(low)
-    if isinstance(low, np.ndarray):
-        low = torch.from_numpy(np.ascontiguousarray(low))
-        if low.dtype == torch.uint8 and low.dim() == 3 and low.shape[-1] == 3:
-            low = low.permute(2, 0, 1)
-    if low.dim() == 4 and low.shape[0] == 1:
-        low = low[0]
-    if low.dim() != 3 or low.shape[0] != 3:
-        raise ValueError(f"input image: expected (3,h,w), got {tuple(low.shape)}")
-    if low.dtype == torch.uint8:
-        return low.to(device).float().div(255)
-    return low.to(device, torch.float32)
+def _image_f32(img, device) -> torch.Tensor:
+    """-> fp32 (3,h,w) on `device`: a float CHW image (or (1,3,h,w)) as it is; a uint8 image (HWC array / PIL image, or a CHW
+    tensor) as ToTensor() converts it, x / 255 by a true division (dividing by a host scalar on the device would multiply by
+    fl(1/255): one ulp off for some levels, which the gamma power carries into the output)"""
+    a = _to_array(img)
+    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+    if t.dtype == torch.uint8 and t.dim() == 3 and t.shape[-1] == 3 and (t.shape[0] != 3 or isinstance(a, np.ndarray)):
+        t = t.permute(2, 0, 1)
+    if t.dim() == 4 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 3 or t.shape[0] != 3:
+        raise ValueError(f"input image: expected (3,h,w) or (h,w,3), got {tuple(t.shape)}")
+    if t.dtype == torch.uint8:
+        return t.to(device).float() / torch.full((), 255.0, dtype=torch.float32, device=device)
+    return t.to(device, torch.float32)
 
 
 # ---- evaluate ---------------------------------------------------------------------------------------------------------
@@ -189,12 +190,121 @@ def _model_device(model):
     raise RuntimeError("evaluate: the model has no parameters")
 
 
+def _plan(sizes, rank, world, batch_size):
+    """The index arithmetic of an evaluation, free of tensors.  `sizes`: (padded shape, crop size) of this rank's images --
+    images rank, rank + world, ... of the input, in that order --, consumed one at a time.  Yields (lo, hi, runs) per batch:
+    the batch is this rank's images lo .. hi - 1, consecutive ones of equal padded shape and at most batch_size of them (it
+    is yielded once the image after it has been seen); runs lists (j, k, rows): the batch's samples j .. k - 1 share a crop
+    size, and `rows` selects their positions in the input -- this rank's images are every world-th one, so consecutive
+    samples are a strided slice."""
+    lo, shape, crops = 0, None, []
+
+    def batch():
+        runs, j = [], 0
+        while j < len(crops):
+            k = j + 1
+            while k < len(crops) and crops[k] == crops[j]:
+                k += 1
+            i0 = rank + (lo + j) * world
+            runs.append((j, k, slice(i0, i0 + (k - j - 1) * world + 1, world)))
+            j = k
+        return lo, lo + len(crops), runs
+    for padded, crop in sizes:
+        if crops and (len(crops) == batch_size or padded != shape):
+            yield batch()
+            lo, crops = lo + len(crops), []
+        shape = padded
+        crops.append(crop)
+    if crops:
+        yield batch()
+
+
 @torch.no_grad()
+def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, alpha, gamma, batch_size, process_group):
+    """The evaluation loop of evaluate() and evaluate_unpaired(), `who` / `noun` naming them in errors.  load(i, item, device)
+    -> (input fp32 (3,h,w), what score needs of the image); trans_attrs: the model.trans attributes set for the run; score(q
+    uint8 (B,3,h,w), [load's second values]) -> one (B,) fp64 device tensor per key; result(alpha=, per_image=, names=,
+    <key>=mean ...) builds the result for one alpha."""
+    device = _model_device(model)
+    if not device.type == "cuda":
+        raise RuntimeError(_NO_CPU)
+    sweep = isinstance(alpha, (list, tuple))
+    alphas = [float(a) for a in alpha] if sweep else [float(alpha)]
+    if not alphas:
+        raise ValueError(f"{who}: empty alpha sweep")
+    n = len(items)
+    if n == 0:
+        raise ValueError(f"{who}: no {noun}")
+    world, rank = 1, 0
+    if process_group is not None or (dist.is_available() and dist.is_initialized()):
+        world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+    use_trunk = sweep and hasattr(model, "trunk")
+    trans = model.trans
+    saved_attrs = {k: getattr(trans, k) for k in ("gated", "alpha_s", "gated2", "alpha")}
+    saved_k = {k: trans.__dict__[k] for k in ("_this_k_host", "_this_k_dev") if k in trans.__dict__}
+    saved_modes = [(m, m.training) for m in model.modules()]
+    # rows: images in input order; columns: keys.  This rank fills the rows of its images, zeros elsewhere.
+    res = torch.zeros((len(alphas), n, len(keys)), dtype=torch.float64, device=device)
+    loaded = []                # this rank's images not yet scored: (padded input, (h, w), load's second); _plan looks one ahead
+
+    def sizes():
+        for i in range(rank, n, world):
+            x, aux = load(i, items[i], device)
+            xp, hw = pad_to_multiple(x.unsqueeze(0), 8)
+            loaded.append((xp, hw, aux))
+            yield xp.shape, hw
+    try:
+        model.eval()
+        for k, v in trans_attrs.items():
+            setattr(trans, k, v)
+        with torch.cuda.device(device):
+            for lo, hi, runs in _plan(sizes(), rank, world, max(1, int(batch_size))):
+                batch = loaded[:hi - lo]
+                del loaded[:hi - lo]
+                x = torch.cat([b[0] for b in batch]) if len(batch) > 1 else batch[0][0]
+                xg = x ** gamma
+                trunk = model.trunk(xg) if use_trunk else None
+                for ai, a in enumerate(alphas):
+                    trans.alpha = a
+                    if trunk is not None:
+                        out = trans.PHVIT_residual(*trunk)
+                    else:
+                        out = model(xg)
+                        if isinstance(out, tuple):               # CIDNet_TNSM: (rgb, noise map or None)
+                            out = out[0]
+                    for j, k, rows in runs:                      # runs of equal crop size share one launch
+                        q = to_uint8(out[j:k], batch[j][1])
+                        into = res[ai, rows]
+                        for col, v in enumerate(score(q, [b[2] for b in batch[j:k]])):
+                            into[:, col].copy_(v)
+        if world > 1:
+            dist.all_reduce(res, op=dist.ReduceOp.SUM, group=process_group)
+        host = res.cpu().numpy()
+    finally:
+        for k, v in saved_attrs.items():
+            setattr(trans, k, v)
+        trans.__dict__.update(saved_k)
+        for m, mode in saved_modes:
+            m.training = mode
+    names = list(getattr(items, "names", range(n)))
+    out = []
+    for ai, a in enumerate(alphas):
+        per = {k: [float(v) for v in host[ai, :, j]] for j, k in enumerate(keys)}
+        means = {}
+        for k, vals in per.items():                               # running sum in input order, / n (measure.py:146-150)
+            acc = 0.0
+            for v in vals:
+                acc += v
+            means[k] = acc / n
+        out.append(result(alpha=a, per_image=per, names=names, **means))
+    return out if sweep else out[0]
+
+
 def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
              alpha=1.0, batch_size: int = 1, process_group=None):
     """eval.py + measure.py on the device.  `pairs`: a sequence of (low, gt) -- low a (3,h,w) float image in [0, 1] (or a
     uint8 HWC image, converted as ToTensor() does), gt uint8 HWC / CHW or a float ToTensor() image of the same size
-    (folder_pairs() yields these).  Each input is reflect-padded to a multiple of 8, run through model(x ** gamma) in eval
+    (folder_pairs() yields these).  Each input is reflect-padded to a multiple of 8, run through model(pow(x, gamma)) in eval
     mode under no_grad with trans.gated / alpha_s / gated2 / alpha set (a tuple result -- CIDNet_TNSM -- gives its [0]),
     clamped, cropped and quantized to uint8, and measured against its ground truth without and with the GT-mean rescale.
 
@@ -205,102 +315,30 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     the per-image values are gathered back into image order with one SUM all-reduce, so every rank returns the same result
     (with batch_size=1 bit-identical to a single process).
     The model's attributes and the train / eval mode of every submodule are restored afterwards."""
-    device = _model_device(model)
-    if not device.type == "cuda":
-        raise RuntimeError(_NO_CPU)
-    sweep = isinstance(alpha, (list, tuple))
-    alphas = [float(a) for a in alpha] if sweep else [float(alpha)]
-    if not alphas:
-        raise ValueError("evaluate: empty alpha sweep")
-    n = len(pairs)
-    if n == 0:
-        raise ValueError("evaluate: no image pairs")
-    world, rank = 1, 0
-    if process_group is not None or (dist.is_available() and dist.is_initialized()):
-        world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
-    batch_size = max(1, int(batch_size))
-    use_trunk = sweep and hasattr(model, "trunk")
-    trans = model.trans
-    saved_attrs = {k: getattr(trans, k) for k in ("gated", "alpha_s", "gated2", "alpha")}
-    saved_k = {k: trans.__dict__[k] for k in ("_this_k_host", "_this_k_dev") if k in trans.__dict__}
-    saved_modes = [(m, m.training) for m in model.modules()]
-    # rows: images in input order; columns: _KEYS.  This rank fills the rows of its images, zeros elsewhere.
-    res = torch.zeros((len(alphas), n, len(_KEYS)), dtype=torch.float64, device=device)
-    try:
-        model.eval()
-        trans.gated, trans.alpha_s, trans.gated2 = bool(gated), float(alpha_s), bool(gated2)
-        with torch.cuda.device(device):
-            batch = []                                           # [(image index, padded input, gt uint8, (h, w))]
-            for i in range(rank, n, world):
-                low, gt = pairs[i]
-                x = _low_f32(low, device)
-                g = _gt_u8(gt, device)
-                if tuple(g.shape) != tuple(x.shape):
-                    raise ValueError(f"evaluate: image {i}: ground truth {tuple(g.shape[1:])} and input {tuple(x.shape[1:])} "
-                                     "differ in size (resizing the ground truth is not supported)")
-                xp, hw = pad_to_multiple(x.unsqueeze(0), 8)
-                if batch and (len(batch) == batch_size or batch[0][1].shape != xp.shape):
-                    _run_batch(model, batch, gamma, alphas, use_trunk, world, res)
-                    batch = []
-                batch.append((i, xp, g, hw))
-            if batch:
-                _run_batch(model, batch, gamma, alphas, use_trunk, world, res)
-        if world > 1:
-            dist.all_reduce(res, op=dist.ReduceOp.SUM, group=process_group)
-        host = res.cpu().numpy()
-    finally:
-        for k, v in saved_attrs.items():
-            setattr(trans, k, v)
-        trans.__dict__.update(saved_k)
-        for m, mode in saved_modes:
-            m.training = mode
-    names = list(getattr(pairs, "names", range(n)))
+    def load(i, pair, device):
+        x, g = _image_f32(pair[0], device), _gt_u8(pair[1], device)
+        if tuple(g.shape) != tuple(x.shape):
+            raise ValueError(f"evaluate: image {i}: ground truth {tuple(g.shape[1:])} and input {tuple(x.shape[1:])} "
+                             "differ in size (resizing the ground truth is not supported)")
+        return x, g
+
+    def score(q, gts):
+        g = torch.stack(gts) if len(gts) > 1 else gts[0].unsqueeze(0)
+        return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True))
     skipped = list(getattr(pairs, "skipped", []))
-    out = []
-    for ai, a in enumerate(alphas):
-        per = {k: [float(v) for v in host[ai, :, j]] for j, k in enumerate(_KEYS)}
-        means = {}
-        for k, vals in per.items():                               # running sum in input order, / n (measure.py:146-150)
-            acc = 0.0
-            for v in vals:
-                acc += v
-            means[k] = acc / n
-        out.append(EvalResult(alpha=a, per_image=per, names=names, skipped=skipped, **means))
-    return out if sweep else out[0]
-
-
-def _run_batch(model, batch, gamma, alphas, use_trunk, world, res):
-    x = torch.cat([b[1] for b in batch]) if len(batch) > 1 else batch[0][1]
-    xg = x ** gamma
-    trunk = model.trunk(xg) if use_trunk else None
-    first = batch[0][0]
-    for ai, a in enumerate(alphas):
-        model.trans.alpha = a
-        if trunk is not None:
-            out = model.trans.PHVIT_residual(*trunk)
-        else:
-            out = model(xg)
-            if isinstance(out, tuple):                           # CIDNet_TNSM: (rgb, noise map or None)
-                out = out[0]
-        j = 0
-        while j < len(batch):                                    # runs of equal crop size share one launch
-            k = j + 1
-            while k < len(batch) and batch[k][3] == batch[j][3]:
-                k += 1
-            h, w = batch[j][3]
-            q = to_uint8(out[j:k], (h, w))
-            g = torch.stack([b[2] for b in batch[j:k]]) if k - j > 1 else batch[j][2].unsqueeze(0)
-            p0, s0 = psnr_ssim(q, g, gt_mean=False)
-            p1, s1 = psnr_ssim(q, g, gt_mean=True)
-            # this rank's images are every world-th one, so consecutive images of a batch are a strided slice of the rows
-            i0 = first + j * world
-            rows = res[ai, i0:i0 + (k - j - 1) * world + 1:world]
-            for col, v in enumerate((p0, s0, p1, s1)):
-                rows[:, col].copy_(v)
-            j = k
+    return _evaluate("evaluate", "image pairs", model, pairs, load,
+                     dict(gated=bool(gated), alpha_s=float(alpha_s), gated2=bool(gated2)), score, _KEYS,
+                     lambda **kw: EvalResult(skipped=skipped, **kw), alpha, gamma, batch_size, process_group)
 
 
 # ---- folder pairing (the one piece of host / disk code) ------------------------------------------------------------
+def _read_rgb(path) -> np.ndarray:
+    """uint8 (h,w,3)"""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im.convert("RGB"))
+
+
 class FolderPairs:
     """Sequence of (low, gt) pairs read from disk on access: low = the low-light image as ToTensor() gives it (fp32 (3,h,w) in
     [0, 1]), gt = the ground truth as uint8 (h,w,3); both through PIL's .convert('RGB').  names: the low images' file names;
@@ -313,13 +351,8 @@ class FolderPairs:
         return len(self.paths)
 
     def __getitem__(self, i):
-        from PIL import Image
         lp, gp = self.paths[i]
-        with Image.open(lp) as im:
-            low = np.array(im.convert("RGB"))
-        with Image.open(gp) as im:
-            gt = np.array(im.convert("RGB"))
-        return torch.from_numpy(low).permute(2, 0, 1).float().div(255), gt
+        return torch.from_numpy(_read_rgb(lp)).permute(2, 0, 1).float().div(255), _read_rgb(gp)
 
 
 def folder_pairs(low_dir: str, high_dir: str) -> FolderPairs:
@@ -563,11 +596,10 @@ class UnpairedResult:
     names: list = field(default_factory=list)
 
 
-@torch.no_grad()
 def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batch_size: int = 1, process_group=None):
     """eval.py --unpaired + measure_niqe_bris.py on the device.  `images`: a sequence of (3,h,w) float images in [0, 1] (or
     uint8 HWC images, converted as ToTensor() does; folder_images() yields these), each at least 96 x 96.  Each is reflect-
-    padded to a multiple of 8, run through model(x ** gamma) in eval mode under no_grad with trans.gated2 = True and
+    padded to a multiple of 8, run through model(pow(x, gamma)) in eval mode under no_grad with trans.gated2 = True and
     trans.alpha = alpha (a tuple result -- CIDNet_TNSM -- gives its [0]), clamped, cropped, quantized to uint8 and scored
     with NIQE.  params: a NiqeParams or the path of the reference's niqe_pris_params.npz.
 
@@ -577,100 +609,15 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
     The model's attributes and the train / eval mode of every submodule are restored afterwards.
     Not reproduced: the JPEG round trip of eval.py's outputs for .jpg inputs, and BRISQUE."""
     prm = _niqe_params(params)
-    device = _model_device(model)
-    if not device.type == "cuda":
-        raise RuntimeError(_NO_CPU)
-    sweep = isinstance(alpha, (list, tuple))
-    alphas = [float(a) for a in alpha] if sweep else [float(alpha)]
-    if not alphas:
-        raise ValueError("evaluate_unpaired: empty alpha sweep")
-    n = len(images)
-    if n == 0:
-        raise ValueError("evaluate_unpaired: no images")
-    world, rank = 1, 0
-    if process_group is not None or (dist.is_available() and dist.is_initialized()):
-        world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
-    batch_size = max(1, int(batch_size))
-    use_trunk = sweep and hasattr(model, "trunk")
-    trans = model.trans
-    saved_attrs = {k: getattr(trans, k) for k in ("gated", "alpha_s", "gated2", "alpha")}
-    saved_k = {k: trans.__dict__[k] for k in ("_this_k_host", "_this_k_dev") if k in trans.__dict__}
-    saved_modes = [(m, m.training) for m in model.modules()]
-    res = torch.zeros((len(alphas), n), dtype=torch.float64, device=device)      # this rank fills its images, zeros elsewhere
-    try:
-        model.eval()
-        trans.gated2 = True
-        with torch.cuda.device(device):
-            batch = []                                           # [(image index, padded input, (h, w))]
-            for i in range(rank, n, world):
-                x = _image_f32(images[i], device)
-                if x.shape[1] < NIQE_BLOCK or x.shape[2] < NIQE_BLOCK:
-                    raise ValueError(f"evaluate_unpaired: image {i} is {x.shape[1]} x {x.shape[2]}; NIQE needs at least "
-                                     f"{NIQE_BLOCK} x {NIQE_BLOCK} pixels")
-                xp, hw = pad_to_multiple(x.unsqueeze(0), 8)
-                if batch and (len(batch) == batch_size or batch[0][1].shape != xp.shape):
-                    _run_unpaired_batch(model, batch, gamma, alphas, use_trunk, world, res, prm)
-                    batch = []
-                batch.append((i, xp, hw))
-            if batch:
-                _run_unpaired_batch(model, batch, gamma, alphas, use_trunk, world, res, prm)
-        if world > 1:
-            dist.all_reduce(res, op=dist.ReduceOp.SUM, group=process_group)
-        host = res.cpu().numpy()
-    finally:
-        for k, v in saved_attrs.items():
-            setattr(trans, k, v)
-        trans.__dict__.update(saved_k)
-        for m, mode in saved_modes:
-            m.training = mode
-    names = list(getattr(images, "names", range(n)))
-    out = []
-    for ai, a in enumerate(alphas):
-        vals = [float(v) for v in host[ai]]
-        acc = 0.0
-        for v in vals:                                            # running sum in input order, / n (measure_niqe_bris.py)
-            acc += v
-        out.append(UnpairedResult(alpha=a, niqe=acc / n, per_image={"niqe": vals}, names=names))
-    return out if sweep else out[0]
 
-
-def _image_f32(img, device) -> torch.Tensor:
-    """-> fp32 (3,h,w) on `device`.  A uint8 image (HWC array / PIL image, or a CHW tensor) becomes ToTensor()'s x / 255 by a
-    true division (dividing by a host scalar on the device would multiply by fl(1/255): one ulp off for some levels, which
-    `x ** gamma` carries into the output); anything else goes through _low_f32."""
-    a = _to_array(img)
-    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
-    if t.dtype != torch.uint8:
-        return _low_f32(a, device)
-    if t.dim() == 3 and t.shape[-1] == 3 and (t.shape[0] != 3 or isinstance(a, np.ndarray)):
-        t = t.permute(2, 0, 1)
-    if t.dim() != 3 or t.shape[0] != 3:
-        raise ValueError(f"input image: expected (3,h,w) or (h,w,3), got {tuple(t.shape)}")
-    return t.to(device).float() / torch.full((), 255.0, dtype=torch.float32, device=device)
-
-
-def _run_unpaired_batch(model, batch, gamma, alphas, use_trunk, world, res, prm):
-    x = torch.cat([b[1] for b in batch]) if len(batch) > 1 else batch[0][1]
-    xg = x ** gamma
-    trunk = model.trunk(xg) if use_trunk else None
-    first = batch[0][0]
-    for ai, a in enumerate(alphas):
-        model.trans.alpha = a
-        if trunk is not None:
-            out = model.trans.PHVIT_residual(*trunk)
-        else:
-            out = model(xg)
-            if isinstance(out, tuple):                           # CIDNet_TNSM: (rgb, noise map or None)
-                out = out[0]
-        j = 0
-        while j < len(batch):                                    # runs of equal crop size share one launch
-            k = j + 1
-            while k < len(batch) and batch[k][2] == batch[j][2]:
-                k += 1
-            q = to_uint8(out[j:k], batch[j][2])
-            i0 = first + j * world
-            res[ai, i0:i0 + (k - j - 1) * world + 1:world].copy_(niqe(q, prm))
-            j = k
+    def load(i, img, device):
+        x = _image_f32(img, device)
+        if x.shape[1] < NIQE_BLOCK or x.shape[2] < NIQE_BLOCK:
+            raise ValueError(f"evaluate_unpaired: image {i} is {x.shape[1]} x {x.shape[2]}; NIQE needs at least "
+                             f"{NIQE_BLOCK} x {NIQE_BLOCK} pixels")
+        return x, None
+    return _evaluate("evaluate_unpaired", "images", model, images, load, dict(gated2=True), lambda q, _: (niqe(q, prm),),
+                     ("niqe",), UnpairedResult, alpha, gamma, batch_size, process_group)
 
 
 class FolderImages:
@@ -684,10 +631,7 @@ class FolderImages:
         return len(self.paths)
 
     def __getitem__(self, i):
-        from PIL import Image
-        with Image.open(self.paths[i]) as im:
-            a = np.array(im.convert("RGB"))
-        return torch.from_numpy(a).permute(2, 0, 1).float().div(255)
+        return torch.from_numpy(_read_rgb(self.paths[i])).permute(2, 0, 1).float().div(255)
 
 
 def folder_images(directory: str) -> FolderImages:

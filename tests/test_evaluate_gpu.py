@@ -2,41 +2,23 @@
 the model's own output, the model is left as it was found, alpha sweeps run the trunk once per batch, the MSSA / TNSM
 variants, evaluation between training steps, and data-parallel sharding over two ranks.
 
-Every case runs in a fresh spawned process (_in_child): the models, trainers and captured graphs built here -- a trainer is
-never freed (its gradient hooks sit on the model's parameters) -- stay out of the pytest process, whose later tests capture
-graphs of their own."""
+Every case runs in a fresh spawned process (tests/evaluate_harness.py: in_child)."""
 import os
-import queue
-import socket
 import sys
-import traceback
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from oracle import cidnet_oracle as O
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import metrics_ref as R  # noqa: E402
+from evaluate_harness import in_child as _in_child, model as _model, two_ranks  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-CHANS = (12, 12, 24, 48)
 # four images that pad to 40 x 56 (three different crops), then two of 32 x 48
 SIZES = [(36, 52), (36, 52), (33, 50), (40, 56), (32, 48), (32, 48)]
-
-
-def _model(cls_name="CIDNet", seed=5):
-    import hvi_cidnet_amd as P
-    m = getattr(P, cls_name)(channels=list(CHANS))
-    variant = {"CIDNet": "base", "CIDNet_MSSA": "mssa", "CIDNet_TNSM": "tnsm"}[cls_name]
-    p = O.make_params(seed, channels=CHANS, variant=variant)
-    m.load_state_dict({k: p[k] for k in m.state_dict().keys()})
-    return m.to("cuda:0")
 
 
 def _pairs(seed=9, sizes=SIZES):
@@ -87,37 +69,6 @@ def _assert_close(res, ref):
         d = np.abs(np.array(res.per_image[k]) - np.array(ref[k])).max()
         assert d <= tol, (k, d)
         assert getattr(res, k) == sum(res.per_image[k]) / len(res.per_image[k])
-
-
-def _child(name, args, q):
-    try:
-        q.put((True, globals()[name](*args)))
-    except BaseException:
-        q.put((False, traceback.format_exc()))
-
-
-def _in_child(fn, *args):
-    """fn(*args) in a fresh spawned process; returns its result, or fails the test with the child's traceback"""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_child, args=(fn.__name__, args, q))
-    p.start()
-    res = None
-    try:
-        for _ in range(100):                                     # <= 500 s; stop waiting once the child has died
-            try:
-                res = q.get(timeout=5)
-                break
-            except queue.Empty:
-                if not p.is_alive():
-                    break
-    finally:
-        p.join(120)
-    assert res is not None and p.exitcode == 0, f"child process exit code {p.exitcode}"
-    ok, val = res
-    if not ok:
-        pytest.fail(val, pytrace=False)
-    return val
 
 
 @pytest.mark.parametrize("cfg", [dict(gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0),
@@ -212,6 +163,21 @@ def _case_variant(cls_name):
     assert m.training
 
 
+def test_uint8_low_scores_like_its_totensor_image(dev):
+    """a uint8 HWC low image is converted as ToTensor() converts it on the host (a true division by 255), on every level"""
+    _in_child(_case_uint8_low)
+
+
+def _case_uint8_low():
+    import hvi_cidnet_amd as P
+    m = _model()
+    h, w = SIZES[0]
+    (_, gt), = _pairs(sizes=SIZES[:1])[0]
+    low8 = np.random.default_rng(3).permutation(np.arange(h * w * 3) % 256).astype(np.uint8).reshape(h, w, 3)
+    as_float = torch.from_numpy(low8).permute(2, 0, 1).float().div(255)
+    assert P.evaluate(m, [(low8, gt)], gamma=1.3) == P.evaluate(m, [(as_float, gt)], gamma=1.3)
+
+
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_evaluation_between_training_steps(dev, use_graph):
     """2 steps, evaluate(trainer.model), 2 steps == 4 steps bit for bit: the evaluation leaves the prepared weights, the
@@ -242,52 +208,17 @@ def _case_between_training_steps(use_graph):
     assert torch.equal(finals[0][2], finals[1][2])
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, HERE)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    import hvi_cidnet_amd as P
-    pairs, _ = _pairs(sizes=SIZES[:5])
-    res = P.evaluate(_model(), pairs, gated=True, alpha=[0.9, 1.0], batch_size=1)
-    q.put((rank, [(r.alpha, r.psnr, r.ssim, r.psnr_gt_mean, r.ssim_gt_mean, r.per_image) for r in res]))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
 @pytest.mark.timeout(600)
 def test_two_ranks_shard_the_evaluation(dev):
     """two ranks sharing the GPU over gloo: rank r measures images i % 2 == r, and both return exactly the
     single-process per-image values and means"""
-    import hvi_cidnet_amd as P
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = {}
-    for _ in range(world):
-        r, v = q.get(timeout=500)
-        got[r] = v
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
-    ref = _in_child(_single_process_reference)
+    got = two_ranks(_case_sweep_of_five)
+    ref = _in_child(_case_sweep_of_five)
     assert got[0] == ref and got[1] == ref
 
 
-def _single_process_reference():
+def _case_sweep_of_five():
     import hvi_cidnet_amd as P
     pairs, _ = _pairs(sizes=SIZES[:5])
-    ref = P.evaluate(_model(), pairs, gated=True, alpha=[0.9, 1.0], batch_size=1)
-    return [(r.alpha, r.psnr, r.ssim, r.psnr_gt_mean, r.ssim_gt_mean, r.per_image) for r in ref]
+    res = P.evaluate(_model(), pairs, gated=True, alpha=[0.9, 1.0], batch_size=1)
+    return [(r.alpha, r.psnr, r.ssim, r.psnr_gt_mean, r.ssim_gt_mean, r.per_image) for r in res]

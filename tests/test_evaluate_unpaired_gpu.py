@@ -5,27 +5,19 @@ trunk once per batch; the MSSA / TNSM variants; two ranks equal one.
 
 Every case runs in a fresh spawned process, as in tests/test_evaluate_gpu.py."""
 import os
-import queue
-import socket
 import sys
-import traceback
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
-
-from oracle import cidnet_oracle as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 import metrics_ref as QR  # noqa: E402
 import niqe_ref as R  # noqa: E402
+from evaluate_harness import in_child as _in_child, model as _model, two_ranks  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-CHANS = (12, 12, 24, 48)
 PARAMS = os.path.join(HERE, "golden", "niqe_pris_params.npz")
 # three images that pad to 200 x 296 (three different crops; the first needs no padding), then two of 192 x 288
 SIZES = [(200, 296), (197, 290), (194, 295), (192, 288), (192, 288)]
@@ -34,15 +26,6 @@ SIZES = [(200, 296), (197, 290), (194, 295), (192, 288), (192, 288)]
 def _bar():
     with np.load(os.path.join(HERE, "golden", "niqe.npz")) as z:
         return 10 * float(z["score_perturb"])
-
-
-def _model(cls_name="CIDNet", seed=5):
-    import hvi_cidnet_amd as P
-    m = getattr(P, cls_name)(channels=list(CHANS))
-    variant = {"CIDNet": "base", "CIDNet_MSSA": "mssa", "CIDNet_TNSM": "tnsm"}[cls_name]
-    p = O.make_params(seed, channels=CHANS, variant=variant)
-    m.load_state_dict({k: p[k] for k in m.state_dict().keys()})
-    return m.to("cuda:0")
 
 
 def _images(seed=9, sizes=SIZES):
@@ -94,37 +77,6 @@ def _assert_close(res, ref):
     assert np.isfinite(want).all(), want
     assert np.abs(got - want).max() <= _bar(), (got, want)
     assert res.niqe == sum(res.per_image["niqe"]) / len(res.per_image["niqe"])
-
-
-def _child(name, args, q):
-    try:
-        q.put((True, globals()[name](*args)))
-    except BaseException:
-        q.put((False, traceback.format_exc()))
-
-
-def _in_child(fn, *args):
-    """fn(*args) in a fresh spawned process; returns its result, or fails the test with the child's traceback"""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_child, args=(fn.__name__, args, q))
-    p.start()
-    res = None
-    try:
-        for _ in range(100):                                     # <= 500 s; stop waiting once the child has died
-            try:
-                res = q.get(timeout=5)
-                break
-            except queue.Empty:
-                if not p.is_alive():
-                    break
-    finally:
-        p.join(120)
-    assert res is not None and p.exitcode == 0, f"child process exit code {p.exitcode}"
-    ok, val = res
-    if not ok:
-        pytest.fail(val, pytrace=False)
-    return val
 
 
 @pytest.mark.parametrize("cfg", [dict(gamma=1.0, alpha=1.0, batch_size=1), dict(gamma=1.3, alpha=0.85, batch_size=2)])
@@ -232,49 +184,16 @@ def _case_small():
     assert m.training
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, HERE)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    import hvi_cidnet_amd as P
-    res = P.evaluate_unpaired(_model(), _images(), PARAMS, alpha=[0.9, 1.0], batch_size=1)
-    q.put((rank, [(r.alpha, r.niqe, r.per_image) for r in res]))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
 @pytest.mark.timeout(600)
 def test_two_ranks_shard_the_evaluation(dev):
     """two ranks sharing the GPU over gloo: rank r scores images i % 2 == r, and both return exactly the single-process
     per-image values and means"""
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = {}
-    for _ in range(world):
-        r, v = q.get(timeout=500)
-        got[r] = v
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
-    ref = _in_child(_single_process_reference)
+    got = two_ranks(_case_sweep_of_all)
+    ref = _in_child(_case_sweep_of_all)
     assert got[0] == ref and got[1] == ref
 
 
-def _single_process_reference():
+def _case_sweep_of_all():
     import hvi_cidnet_amd as P
-    ref = P.evaluate_unpaired(_model(), _images(), PARAMS, alpha=[0.9, 1.0], batch_size=1)
-    return [(r.alpha, r.niqe, r.per_image) for r in ref]
+    res = P.evaluate_unpaired(_model(), _images(), PARAMS, alpha=[0.9, 1.0], batch_size=1)
+    return [(r.alpha, r.niqe, r.per_image) for r in res]

@@ -1,5 +1,6 @@
 """CPU checks of the evaluation metrics: the fp64 restatement the GPU tests compare against (tests/metrics_ref.py),
-folder_pairs' file pairing, and the refusal of CPU tensors."""
+folder_pairs' file pairing, the refusal of CPU tensors, the input converter's shapes, and the index arithmetic of an
+evaluation (batches, runs of equal crop size, the rows they fill) against the per-image loop."""
 import math
 import os
 import sys
@@ -89,3 +90,62 @@ def test_metrics_refuse_cpu_tensors():
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         P.evaluate(m, [(torch.rand(3, 16, 16), np.zeros((16, 16, 3), np.uint8))])
     assert m.training                                    # nothing was touched
+
+
+def test_input_converter_accepts_and_refuses():
+    """the one input converter on a CPU device: the shapes (the rounding of uint8 inputs needs the GPU: test_metrics_gpu.py)"""
+    from hvi_cidnet_amd import metrics as M
+    a = np.random.default_rng(4).integers(0, 256, (3, 5, 3), dtype=np.uint8)      # HWC although its first axis is 3 too
+    want = torch.from_numpy(a).permute(2, 0, 1).float().div(255)
+    chw8 = torch.from_numpy(a).permute(2, 0, 1).contiguous()
+    for img in (a, chw8, chw8[None], want, want[None], want.double().numpy()):
+        got = M._image_f32(img, "cpu")
+        assert got.dtype == torch.float32 and torch.equal(got, want)
+    assert torch.equal(M._image_f32(torch.zeros(7, 5, 3, dtype=torch.uint8), "cpu"), torch.zeros(3, 7, 5))
+    for bad in (torch.rand(6, 5), torch.rand(4, 6, 5), torch.rand(2, 3, 6, 5), torch.rand(6, 5, 3), np.zeros((6, 5), np.uint8),
+                np.zeros((6, 5, 4), np.uint8), np.zeros((1, 6, 5, 3), np.uint8), torch.zeros(1, 6, 5, dtype=torch.uint8),
+                torch.zeros(2, 3, 6, 5, dtype=torch.uint8)):
+        with pytest.raises(ValueError, match=r"input image: expected \(3,h,w\) or \(h,w,3\), got"):
+            M._image_f32(bad, "cpu")
+
+
+# sizes (h, w) of the images; each pads to a multiple of 8.  The first list is tests/test_evaluate_gpu.py's SIZES.
+PLAN_SIZES = [[(36, 52), (36, 52), (33, 50), (40, 56), (32, 48), (32, 48)],
+              [(40, 56), (40, 56), (48, 56), (48, 56), (48, 56), (47, 56), (40, 56)],   # the padded shape changes inside a batch
+              [(200, 296), (197, 290), (194, 295), (192, 288), (192, 288)],
+              [(33, 50)] * 9, [(33, 50), (40, 56)]]                                        # the last is shorter than world = 3
+
+
+@pytest.mark.parametrize("sizes", PLAN_SIZES)
+@pytest.mark.parametrize("batch_size", [1, 2, 3, 8])
+@pytest.mark.parametrize("world", [1, 2, 3])
+def test_evaluation_plan(sizes, batch_size, world):
+    """metrics._plan against the per-image loop: which images a rank's batches and runs hold, and which rows they fill"""
+    from hvi_cidnet_amd import metrics as M
+    n = len(sizes)
+    padded = [(1, 3, -(-h // 8) * 8, -(-w // 8) * 8) for h, w in sizes]
+    seen = []
+    for rank in range(world):
+        mine = list(range(rank, n, world))
+        batches = list(M._plan(((padded[i], sizes[i]) for i in mine), rank, world, batch_size))
+        # the obvious loop: an image joins the current batch unless that is full or of another padded shape
+        want, cur = [], []
+        for i in mine:
+            if cur and (len(cur) == batch_size or padded[cur[0]] != padded[i]):
+                want.append(cur)
+                cur = []
+            cur.append(i)
+        want += [cur] if cur else []
+        assert [mine[lo:hi] for lo, hi, _ in batches] == want
+        order = []
+        for (lo, hi, runs), imgs in zip(batches, want):
+            assert 1 <= len(imgs) <= batch_size and len({padded[i] for i in imgs}) == 1
+            assert [j for j, _, _ in runs] + [len(imgs)] == [0] + [k for _, k, _ in runs]        # the runs tile the batch
+            for j, k, rows in runs:
+                assert len({sizes[i] for i in imgs[j:k]}) == 1
+                assert k == len(imgs) or sizes[imgs[k]] != sizes[imgs[j]]                          # and are maximal
+                assert list(range(n))[rows] == imgs[j:k]
+                order += imgs[j:k]
+        assert order == mine                                                                     # ascending within a rank
+        seen += order
+    assert sorted(seen) == list(range(n))                                                         # every image exactly once

@@ -117,3 +117,15 @@ def test_shape_checks(dev):
         M.psnr(a.float(), a.float())
     with pytest.raises(RuntimeError, match="differ"):
         M.psnr(a, a[:, :, :, :20])
+
+
+def test_uint8_input_is_divided_by_255(dev):
+    """the input converter on all 256 levels: a uint8 HWC array and a uint8 CHW tensor become, bit for bit, what ToTensor()
+    computes on the host.  (`t.float().div(255)` on the device multiplies by fl(1/255) instead: DESIGN.md 6.1)"""
+    M = P_M()
+    a = np.arange(256, dtype=np.uint8).repeat(3).reshape(16, 16, 3)
+    want = torch.from_numpy(a).permute(2, 0, 1).float().div(255)
+    for img in (a, torch.from_numpy(a).permute(2, 0, 1).contiguous()):
+        got = M._image_f32(img, dev)
+        assert got.is_cuda and got.dtype == torch.float32 and tuple(got.shape) == (3, 16, 16)
+        assert torch.equal(got.cpu(), want)
