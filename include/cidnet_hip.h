@@ -11,7 +11,7 @@
  *   - all tensors are fp32, NCHW-contiguous device memory unless a stride argument says otherwise;
  *     "HW" planes are H*W floats; pointers are plain device pointers owned by the caller;  the one
  *     exception are the evaluation metrics (cidnet_metric_*), whose images are uint8 (B,3,h,w) and
- *     whose results are fp64 device buffers;
+ *     whose results are fp64 device buffers, and the training-batch kernel (cidnet_augment_*), which reads a uint8 arena;
  *   - `stream` is a hipStream_t passed as void* (the caller's current stream; NULL = default);
  *   - functions are stateless and re-entrant, never allocate, never synchronise and never copy to
  *     the host, so a caller may capture them into a hipGraph;  scratch memory comes in through
@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 8
+#define CIDNET_ABI_VERSION 9
 
 int cidnet_abi_version(void);
 
@@ -524,6 +524,21 @@ int cidnet_metric_niqe_fit(const double* moments, const double* tables, int bloc
 long cidnet_metric_niqe_ws_floats(int B, int h, int w);
 int cidnet_metric_niqe_features(const uint8_t* rgb, const double* window, const double* tables, double* feat, float* ws,
                                 long ws_floats, int B, int h, int w, void* stream);
+
+/* ---- Training batches from a resident uint8 set (data/data.py:6-12 transform1 + train.py:54-56 of the reference): random
+ * crop, horizontal / vertical flip, ToTensor and the gamma power of one batch, low image and ground truth, in one launch.
+ * arena: uint8 device memory holding every image of the set as planar (3,h,w).  plan: B rows of 8 int64 words on the device:
+ *   byte offset of the low image in the arena | byte offset of its ground truth | h | w | y0 | x0 | flips (bit 0 horizontal,
+ *   bit 1 vertical) | 0.  x, gt: (B,3,Sh,Sw) fp32.  With yy = y0 + (vflip ? Sh-1-i : i), xx = x0 + (hflip ? Sw-1-j : j):
+ *   gt[s,c,i,j] = fp32(high[c,yy,xx]) / 255.0f, a correctly rounded division (ToTensor);
+ *   x[s,c,i,j] = table[low[c,yy,xx]], table = 256 fp32 values on the device, pow(q / 255, gamma) per level as the caller
+ *   rounded it (hvi-cidnet_amd/data.py: fp64 pow, rounded once); table == NULL: the quotient itself (gamma off).
+ * Only bytes inside the crop windows are read.  The plan lives on the device and cannot be checked here without a copy:
+ * EVERY ROW MUST HAVE BEEN RANGE-CHECKED ON THE HOST WHERE IT WAS MADE (0 <= y0 <= h-Sh, 0 <= x0 <= w-Sw, both images inside
+ * the arena).  B * 3 > 65535 is CIDNET_ERR_SHAPE.  A value depends on its plan row alone: bit-identical from call to call
+ * and independent of the rest of the batch. */
+int cidnet_augment_crop_flip(const uint8_t* arena, const long* plan, const float* table, float* x, float* gt, int B, int Sh,
+                             int Sw, void* stream);
 
 #ifdef __cplusplus
 }
