@@ -27,6 +27,7 @@ from __future__ import annotations
 from typing import Callable, List, Optional
 
 import contextlib
+import math
 import os
 
 import torch
@@ -39,33 +40,140 @@ def _default_loss(out, gt):
 
 
 class FlatAdam:
-    """torch.optim.Adam semantics on one flat buffer; `kernel` selects the fused HIP update."""
+    """torch.optim.Adam semantics on one flat buffer; `kernel` selects the fused HIP update.
 
-    def __init__(self, flat_p, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, kernel: bool = True):
+    max_grad_norm / skip_nonfinite / device_state: any of them selects the device-state path -- the step count lives on the
+    device (`state`: applied, skipped), and every step runs the guard first (ops.grad_guard: fp64 norm of the averaged
+    gradient, clip_grad_norm_'s coefficient, skip when the gradient holds a NaN or an Inf and skip_nonfinite is set), then an
+    Adam update that reads the guard's record; nothing of it reaches the host.  With all three off this is the plain update
+    with a host step count.  kernel=False restates the same decisions in torch (CPU tests; it synchronises)."""
+
+    def __init__(self, flat_p, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, kernel: bool = True,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, device_state: bool = False):
         self.p = flat_p
         self.m = torch.zeros_like(flat_p)
         self.v = torch.zeros_like(flat_p)
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.t = 0
         self.kernel = kernel
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = bool(device_state) or self.skip_nonfinite or max_grad_norm is not None
+        if self.guarded:
+            self.state = torch.zeros(2, dtype=torch.int64, device=flat_p.device)       # steps applied, steps skipped
+            self.record = torch.zeros(4, dtype=torch.float32, device=flat_p.device)    # apply, scale, 1 - b1^t, sqrt(1 - b2^t)
 
-    def step(self, flat_g, n_live: int, grad_scale: float = 1.0):
-        self.t += 1
+    def _clips(self):
+        c = self.max_grad_norm
+        return c is not None and c > 0 and c != float("inf")
+
+    def steps_applied(self) -> int:
+        """updates applied so far (device-state path: reads the device, so it waits for the queued steps)"""
+        return int(self.state[0].item()) if self.guarded else self.t
+
+    def steps_skipped(self) -> int:
+        """steps the guard skipped so far (synchronises as steps_applied)"""
+        return int(self.state[1].item()) if self.guarded else 0
+
+    def set_counts(self, applied: int, skipped: int = 0):
+        if self.guarded:
+            self.state.copy_(torch.tensor([int(applied), int(skipped)], dtype=torch.int64))
+        else:
+            self.t = int(applied)
+
+    def step(self, flat_g, n_live: int, grad_scale: float = 1.0, loss=None, log_row=None):
+        """loss (the step's scalar) and log_row (a device address for the kernel path, a (4,) fp64 tensor for the torch
+        restatement) only matter on the device-state path: the guard writes loss, norm, coef and the signed count there."""
         b1, b2 = self.betas
         p, g, m, v = self.p[:n_live], flat_g[:n_live], self.m[:n_live], self.v[:n_live]
+        if self.guarded:
+            return self._guarded_step(p, g, m, v, grad_scale, loss, log_row)
+        self.t += 1
         if self.kernel:
             from . import ops
             ops.adam_step(p, g, m, v, self.lr, b1, b2, self.eps, self.wd, self.t, grad_scale)
             return
         # plain-torch restatement of the same update (used by the CPU/gloo tests of the harness only)
-        g = g * grad_scale
+        self._torch_update(p, g, m, v, grad_scale, self.t)
+
+    def _torch_update(self, p, g, m, v, gscale, t):
+        b1, b2 = self.betas
+        g = g * gscale
         if self.wd:
             g = g + self.wd * p
         m.mul_(b1).add_(g, alpha=1 - b1)
         v.mul_(b2).addcmul_(g, g, value=1 - b2)
-        bc1 = 1 - b1 ** self.t
-        bc2 = 1 - b2 ** self.t
+        bc1 = 1 - b1 ** t
+        bc2 = 1 - b2 ** t
         p.sub_((self.lr / bc1) * (m / (v.sqrt() / bc2 ** 0.5 + self.eps)))
+
+    def _guarded_step(self, p, g, m, v, grad_scale, loss, log_row):
+        b1, b2 = self.betas
+        if self.kernel:
+            from . import ops
+            if loss is not None and not (loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1):
+                raise RuntimeError("the guarded step logs a scalar fp32 device loss")
+            ops.grad_guard(g, grad_scale, self.max_grad_norm if self._clips() else None, self.skip_nonfinite, b1, b2, loss,
+                           self.state, self.record, log_row)
+            ops.adam_step_dev(p, g, m, v, self.lr, b1, b2, self.eps, self.wd, self.record)
+            return
+        # plain-torch restatement of the guard's decisions (CPU/gloo tests; reads the sum on the host)
+        ss = float(g.double().pow(2).sum().item())
+        norm = math.sqrt(ss) * grad_scale if ss == ss and ss >= 0 else float("nan")
+        coef = 1.0
+        if self._clips():
+            coef = self.max_grad_norm / (norm + 1e-6)
+            if coef > 1.0:
+                coef = 1.0
+        apply = math.isfinite(ss) or not self.skip_nonfinite
+        self.state[0 if apply else 1] += 1
+        applied = int(self.state[0].item())
+        if log_row is not None:
+            log_row.copy_(torch.tensor([float(loss) if loss is not None else float("nan"), norm, coef,
+                                        applied if apply else -(applied + 1)], dtype=torch.float64))
+        if apply:
+            self._torch_update(p, g, m, v, grad_scale * coef, applied)
+
+
+class StepLog:
+    """A (capacity, 4) fp64 device buffer the guarded step writes one row into: loss, gradient norm, clip coefficient, and
+    the applied-step count after the step (negative, -(count + 1), when the step was skipped).  Step i since the last
+    reset() writes row i % capacity; the row index is a host integer -- the host knows how many steps it issued whether or
+    not they were applied.  read() is the only transfer: one device-to-host copy."""
+    LOSS, NORM, COEF, COUNT = 0, 1, 2, 3
+
+    def __init__(self, capacity: int):
+        self.capacity = int(capacity)
+        if self.capacity <= 0:
+            raise ValueError("StepLog: capacity must be positive")
+        self.buf = None
+        self.issued = 0
+
+    def bind(self, device):
+        """allocate the buffer on `device` (the trainer does this when it builds its arena)"""
+        if self.buf is None or self.buf.device != torch.device(device):
+            self.buf = torch.zeros((self.capacity, 4), dtype=torch.float64, device=device)
+        return self
+
+    def reset(self):
+        self.issued = 0
+
+    def next_row(self):
+        """-> the row tensor of the step that is issued now"""
+        row = self.buf[self.issued % self.capacity]
+        self.issued += 1
+        return row
+
+    def read(self):
+        """rows written since reset() (the last `capacity` of them when more were issued), in step order, as a numpy array"""
+        import numpy as np
+        n = min(self.issued, self.capacity)
+        if n == 0 or self.buf is None:
+            return np.zeros((0, 4), dtype=np.float64)
+        rows = self.buf[:n].cpu().numpy()
+        if self.issued > self.capacity:
+            rows = np.roll(rows, -(self.issued % self.capacity), axis=0)
+        return rows
 
 
 def rank_cpu_set(cpus, local_rank: int, local_world: int):
@@ -104,8 +212,13 @@ class DataParallelTrainer:
                  weight_decay: float = 0.0, n_buckets: int = 4, loss_fn: Optional[Callable] = None,
                  process_group=None, use_hip_kernels: bool = True, wgrad_stream: bool = True, use_graph: bool = False,
                  max_steps_in_flight: int = 3, max_queued_bytes: Optional[int] = None,
-                 prepared_weights: Optional[bool] = None):
+                 prepared_weights: Optional[bool] = None, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False, step_log: Optional[StepLog] = None):
+        """max_grad_norm / skip_nonfinite / step_log: the guarded step (FlatAdam's device-state path).  The guard runs after
+        the all-reduce, where every rank holds the same gradient, so every rank takes the same decision without talking;
+        step_log (a StepLog) receives one row per step."""
         self.model = model
+        self.step_log = step_log
         self.prepared_weights = (os.environ.get("CIDNET_PREPARED_WEIGHTS", "1") == "1") if prepared_weights is None else bool(prepared_weights)
         # Back-pressure.  Nothing in a training step synchronises host and device, and the host enqueues a step in ~13 ms
         # while the GPU needs ~31 ms.  Root cause of the multi-second stalls of round 1 (tools/stall_probe.py,
@@ -133,7 +246,9 @@ class DataParallelTrainer:
         # weight-gradient GEMMs on a third stream (they feed nothing but the optimizer): 35.9 -> 34.4 ms/step at
         # bs=8 400x600 -- the data-gradient chain of short, latency-bound launches no longer waits behind them
         self.wgrad_stream = wgrad_stream
-        self._opt_args = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._opt_args = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                              skip_nonfinite=skip_nonfinite, device_state=step_log is not None)
+        self._pending_state = None
         self._ready = False
         self._handles: List = []
         self._launch_stream = None
@@ -242,7 +357,12 @@ class DataParallelTrainer:
         for p in live:
             p.register_post_accumulate_grad_hook(self._on_grad)
         self.opt = FlatAdam(self.flat_p, kernel=self.use_hip, **self._opt_args)
+        if self.step_log is not None:
+            self.step_log.bind(dev)
         self._ready = True
+        if self._pending_state is not None:
+            state, self._pending_state = self._pending_state, None
+            self._apply_state(state)
 
     def _check_layout_across_ranks(self, layout, n_live):
         """Every rank derives the arena layout from its OWN probing backward (gradient-ready order).  The order is a
@@ -416,7 +536,7 @@ class DataParallelTrainer:
         self._graph.replay()
         if self.world > 1 or self._force_comm:
             dist.all_reduce(self.flat_g[:self.n_live], op=dist.ReduceOp.SUM, group=self.pg)
-        self.opt.step(self.flat_g, self.n_live, grad_scale=1.0 / self.world)
+        self._opt_step(self._gloss)
         self._weights_changed()          # the captured pass reads prepared operands that the eager passes before it created
         return self._gloss
 
@@ -441,14 +561,89 @@ class DataParallelTrainer:
             for h in self._handles:
                 h.wait()
             self._join_wgrad_stream()
-            self.opt.step(self.flat_g, self.n_live, grad_scale=1.0 / self.world)
-            self._weights_changed()
+            self._opt_step(loss)
+            self._weights_changed()          # also after a skipped step: the host cannot know and must not ask
             loss = loss.detach()
         if x.is_cuda:
             ev = torch.cuda.Event()
             ev.record()
             self._step_events.append(ev)
         return loss
+
+    def _opt_step(self, loss):
+        """fused Adam on the arena; guarded: the guard's two launches first, fed the loss tensor the step returns"""
+        if not self.opt.guarded:
+            self.opt.step(self.flat_g, self.n_live, grad_scale=1.0 / self.world)
+            return
+        row = self.step_log.next_row() if self.step_log is not None else None
+        if row is not None and self.opt.kernel:
+            row = row.data_ptr()
+        self.opt.step(self.flat_g, self.n_live, grad_scale=1.0 / self.world, loss=loss.detach(), log_row=row)
+
+    # ---- optimizer state ----------------------------------------------------------------------------
+    def _live_named(self):
+        """(name, offset, numel, shape) of every parameter the optimizer updates, in arena order"""
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        out = []
+        for p in self.params:
+            off, n = self._slices[id(p)]
+            if off < self.n_live:
+                out.append((names[id(p)], off, n, tuple(p.shape)))
+        return sorted(out, key=lambda r: r[1])
+
+    def state_dict(self):
+        """Adam's state, keyed by parameter NAME (arena offsets follow the gradient-ready order probed at run time): exp_avg
+        and exp_avg_sq per live parameter as CPU tensors, the applied / skipped step counts, lr, betas, eps, weight_decay.
+        Parameters that get no gradient (I_LCA5.*) have no entry.  Synchronises."""
+        if not self._ready:
+            if self._pending_state is not None:
+                return self._pending_state
+            raise RuntimeError("state_dict: the optimizer exists after the first step (or after load_state_dict)")
+        o = self.opt
+        return {"exp_avg": {n: o.m[off:off + c].view(shp).cpu().clone() for n, off, c, shp in self._live_named()},
+                "exp_avg_sq": {n: o.v[off:off + c].view(shp).cpu().clone() for n, off, c, shp in self._live_named()},
+                "steps_applied": o.steps_applied(), "steps_skipped": o.steps_skipped(), "lr": float(o.lr),
+                "betas": tuple(float(b) for b in o.betas), "eps": float(o.eps), "weight_decay": float(o.wd)}
+
+    def load_state_dict(self, state):
+        """Strict: the names must be exactly the live parameters, the shapes theirs.  Before the first step the state is
+        checked against the model's names and shapes and applied once the arena exists; which parameters are live is only
+        known then, so a missing or dead name raises there.  lr, betas, eps and weight decay are taken over at once."""
+        for k in ("exp_avg", "exp_avg_sq", "steps_applied", "steps_skipped", "lr", "betas", "eps", "weight_decay"):
+            if k not in state:
+                raise KeyError(f"load_state_dict: missing entry '{k}'")
+        shapes = {n: tuple(p.shape) for n, p in self.model.named_parameters()}
+        for k in ("exp_avg", "exp_avg_sq"):
+            for n, t in state[k].items():
+                if n not in shapes:
+                    raise KeyError(f"load_state_dict: {k} has an entry for '{n}', which is no parameter of the model")
+                if tuple(t.shape) != shapes[n]:
+                    raise ValueError(f"load_state_dict: {k}['{n}'] has shape {tuple(t.shape)}, the parameter {shapes[n]}")
+        if set(state["exp_avg"]) != set(state["exp_avg_sq"]):
+            raise KeyError("load_state_dict: exp_avg and exp_avg_sq name different parameters")
+        # the hyper-parameters take effect now, so a set_lr() that follows this call wins in either order of events; the
+        # moments and counts need the arena
+        betas, eps, wd = tuple(float(b) for b in state["betas"]), float(state["eps"]), float(state["weight_decay"])
+        self._opt_args.update(betas=betas, eps=eps, weight_decay=wd)
+        if getattr(self, "opt", None) is not None:
+            self.opt.betas, self.opt.eps, self.opt.wd = betas, eps, wd
+        self.set_lr(state["lr"])
+        if self._ready:
+            self._apply_state(state)
+        else:
+            self._pending_state = state
+
+    def _apply_state(self, state):
+        live = self._live_named()
+        want, got = {n for n, *_ in live}, set(state["exp_avg"])
+        if want != got:
+            raise KeyError(f"load_state_dict: missing {sorted(want - got)[:5]}, unexpected {sorted(got - want)[:5]} "
+                           f"({len(want - got)} / {len(got - want)} names)")
+        o = self.opt
+        for n, off, c, shp in live:
+            o.m[off:off + c].copy_(state["exp_avg"][n].reshape(-1))
+            o.v[off:off + c].copy_(state["exp_avg_sq"][n].reshape(-1))
+        o.set_counts(state["steps_applied"], state["steps_skipped"])
 
     def _weights_changed(self):
         if self._prep is not None and self.flat_p.is_cuda:

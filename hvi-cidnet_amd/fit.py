@@ -1,0 +1,151 @@
+"""The training run: the epoch loop of the reference's train.py:195-274 over the pieces this package already has --
+data.TrainBatches (the batches), dp.DataParallelTrainer (the step, here with its guard), schedule.WarmupCosineLR (the
+learning rate of every epoch), metrics.evaluate (validation) and the reference's checkpoint format.
+
+    from hvi_cidnet_amd import CIDNet, CIDNetLoss, ResidentPairs, TrainBatches, fit, folder_pairs
+    model = CIDNet().to(device)
+    pairs = ResidentPairs.from_folders(low_dir, high_dir, device)
+    batches = TrainBatches(pairs, batch_size=8, crop=256, seed=0, gamma=(60, 120))
+    records = fit(model, batches, nEpochs=1000, lr=1e-4, loss_fn=CIDNetLoss(model), max_grad_norm=1.0,
+                  val_pairs=folder_pairs(val_low, val_high), out_dir="weights/train", on_epoch=print)
+
+Inside an epoch the host never waits for the device except through the trainer's own back-pressure: the loss, the gradient
+norm, the clip coefficient and the apply / skip decision of every step are written by the guard into a device-resident step
+log (dp.StepLog) that is read once, after the epoch's last step.
+
+What differs from the reference's loop:
+  * the reference calls clip_grad_norm_ BEFORE zero_grad() / backward() (train.py:68-73), so it clips the previous step's
+    gradients and changes nothing; here the clip sits between the backward and the update, and a step whose gradient holds
+    a NaN or an Inf is skipped on the device (skip_nonfinite) instead of poisoning the weights and both Adam moments;
+  * `resume=` continues a run exactly (Adam moments, step counts, schedule position); the reference's own resume
+    (`start_epoch` > 0: weights only, fresh Adam, restarted warm-up, shortened cosine period) is kept as it is;
+  * left out: the per-epoch training/test.png dump, the metrics .md table (on_epoch hands the numbers to the caller), the
+    option parser, the cyclic scheduler variant, LPIPS (metrics.py), the folder sampling of SICE / SID / LOL-blur.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+from .dp import DataParallelTrainer, StepLog
+from .schedule import WarmupCosineLR
+
+_SCHEDULE_KEYS = ("nEpochs", "lr", "warmup_epochs", "start_warmup", "start_epoch")
+
+
+def run_epoch(trainer, batches, epoch, step_log):
+    """The steps of one epoch and ONE read of the step log -> its rows, (steps, 4) fp64 (dp.StepLog's columns)"""
+    step_log.reset()
+    for x, gt in batches.epoch(epoch):
+        trainer.step(x, gt)
+    return step_log.read()
+
+
+def epoch_stats(rows):
+    """The record entries that come out of an epoch's step log; the loss is the fp64 mean, summed in step order, of the
+    applied steps' losses (NaN when none was applied)"""
+    applied = rows[:, StepLog.COUNT] > 0
+    total = 0.0
+    for v in rows[applied, StepLog.LOSS]:
+        total += float(v)
+    n = int(applied.sum())
+    norms = rows[:, StepLog.NORM]
+    finite = norms[np.isfinite(norms)]
+    return {"steps": int(rows.shape[0]), "skipped": int(rows.shape[0]) - n, "loss": total / n if n else float("nan"),
+            "grad_norm_max": float(finite.max()) if finite.size else float("nan"),
+            "clipped": int((rows[applied, StepLog.COEF] < 1.0).sum())}
+
+
+def _model_device(model):
+    for p in model.parameters():
+        return p.device
+    raise RuntimeError("fit: the model has no parameters")
+
+
+def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, start_epoch=0, snapshots=10, loss_fn=None,
+        max_grad_norm=None, skip_nonfinite=True, val_pairs=None, val_args=None, out_dir=None, resume=None,
+        process_group=None, on_epoch=None, trainer_args=None):
+    """Train `model` for the epochs start_epoch + 1 ... start_epoch + nEpochs and return one record per epoch.
+
+    batches: anything with __len__ (steps per epoch) and epoch(e) yielding (x, gt): data.TrainBatches.
+    The learning rate of the k-th epoch of this run (k = 0, 1, ...) is WarmupCosineLR(lr, nEpochs, warmup_epochs,
+    start_epoch, start_warmup).lr_after(k): the reference constructs its scheduler, trains an epoch, then steps it, so with
+    warm-up the first epoch runs at lr 0 (schedule.py lists the quirks); past the reference's single cosine period the
+    schedule is undefined and raises, as the reference fails there.
+    Every `snapshots` epochs rank 0 writes, into out_dir, epoch_{epoch}.pth (the model's state_dict(), what the reference
+    loads with strict=True) and epoch_{epoch}.train.pt (the trainer's state_dict(), the epoch, the position in the schedule
+    and the arguments that fix it); then, when val_pairs is given, metrics.evaluate(model, val_pairs, **val_args) runs and
+    the record gains psnr / ssim.
+    Record: epoch, lr, steps, skipped, loss (mean over the applied steps, see epoch_stats; averaged over the ranks with one
+    all-reduce per epoch), grad_norm_max, clipped (applied steps with coef < 1).  on_epoch(record) runs on every rank.
+    start_epoch > 0 is the reference's resume: the caller loads weights, Adam starts fresh, the warm-up restarts.
+    resume = path of an epoch_*.train.pt: the exact one.  The trainer's state and the epoch counter come from the file, the
+    model's weights from the epoch_*.pth beside it, the schedule continues where it was (its arguments must be the file's);
+    since data.epoch_plan is a function of (seed, epoch) and every reduction of a step has a fixed order, the run continues
+    bit-identically.  trainer_args: further DataParallelTrainer arguments."""
+    sched_args = dict(nEpochs=int(nEpochs), lr=float(lr), warmup_epochs=int(warmup_epochs), start_warmup=bool(start_warmup),
+                      start_epoch=int(start_epoch))
+    sched = WarmupCosineLR(sched_args["lr"], sched_args["nEpochs"], sched_args["warmup_epochs"], sched_args["start_epoch"],
+                           sched_args["start_warmup"])
+    snapshots = int(snapshots)
+    if snapshots <= 0:
+        raise ValueError("fit: snapshots must be positive")
+    if len(batches) <= 0:
+        raise ValueError("fit: an epoch without steps")
+    log = StepLog(len(batches))
+    trainer = DataParallelTrainer(model, lr=sched.lr_after(0), loss_fn=loss_fn, process_group=process_group,
+                                  max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, step_log=log,
+                                  **(trainer_args or {}))
+    first, done = sched_args["start_epoch"] + 1, 0
+    if resume is not None:
+        saved = torch.load(resume, map_location="cpu", weights_only=False)
+        for k in _SCHEDULE_KEYS:
+            if saved["schedule"][k] != sched_args[k]:
+                raise ValueError(f"fit: resume file was written with {k} = {saved['schedule'][k]!r}, this call has {sched_args[k]!r}")
+        weights = os.path.join(os.path.dirname(os.path.abspath(resume)), saved["weights"])
+        model.load_state_dict(torch.load(weights, map_location="cpu"), strict=True)
+        trainer.load_state_dict(saved["trainer"])
+        first, done = int(saved["epoch"]) + 1, int(saved["epochs_done"])
+    rank, world = trainer.rank, trainer.world
+    if out_dir is not None and rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+    records = []
+    for epoch in range(first, sched_args["start_epoch"] + sched_args["nEpochs"] + 1):
+        lr_now = sched.apply(trainer, done)
+        model.train()
+        rows = run_epoch(trainer, batches, epoch, log)
+        done += 1
+        rec = {"epoch": epoch, "lr": lr_now, **epoch_stats(rows)}
+        if world > 1:
+            t = torch.tensor([rec["loss"]], dtype=torch.float64, device=_model_device(model))
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)
+            rec["loss"] = float(t.item()) / world
+        if epoch % snapshots == 0:
+            if out_dir is not None and rank == 0:
+                _snapshot(model, trainer, out_dir, epoch, done, sched_args)
+            if val_pairs is not None:
+                res = _validate(model, val_pairs, val_args, process_group)
+                rec["psnr"], rec["ssim"] = res.psnr, res.ssim
+        records.append(rec)
+        if on_epoch is not None:
+            on_epoch(rec)
+    return records
+
+
+def _validate(model, val_pairs, val_args, process_group):
+    from . import metrics
+    kw = dict(val_args or {})
+    if process_group is not None:
+        kw.setdefault("process_group", process_group)
+    res = metrics.evaluate(model, val_pairs, **kw)
+    return res[0] if isinstance(res, list) else res
+
+
+def _snapshot(model, trainer, out_dir, epoch, done, sched_args):
+    name = f"epoch_{epoch}.pth"
+    torch.save({k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, os.path.join(out_dir, name))
+    torch.save({"trainer": trainer.state_dict(), "epoch": int(epoch), "epochs_done": int(done), "schedule": dict(sched_args),
+                "weights": name}, os.path.join(out_dir, f"epoch_{epoch}.train.pt"))

@@ -1463,6 +1463,34 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=
                _f(weight_decay), int(step), _f(grad_scale), _stream())
 
 
+GUARD_STATE_WORDS, GUARD_RECORD_FLOATS, GUARD_LOG_COLS = 2, 4, 4      # include/cidnet_hip.h: cidnet_grad_guard
+
+
+def grad_guard(g, grad_scale, max_norm, skip_nonfinite, beta1, beta2, loss, state, record, log_row_ptr=None):
+    """cidnet_grad_guard on the current stream: fp64 norm of g, clip coefficient, apply / skip -> `state` (2 int64), `record`
+    (4 fp32) and, when given, the 4 fp64 values at device address `log_row_ptr`.  max_norm None: no clipping.  loss: the
+    step's 0-dim fp32 device tensor or None.  Launches two kernels, copies nothing."""
+    _check(g, record)
+    if not g.is_contiguous():
+        raise RuntimeError("grad_guard: the gradient must be one contiguous buffer")
+    if loss is not None:
+        _check(loss)
+    if not (state.is_cuda and state.dtype == torch.int64 and state.numel() >= GUARD_STATE_WORDS):
+        raise RuntimeError("grad_guard: state must be an int64 device tensor of 2 elements")
+    n = _raw("cidnet_grad_guard_ws_doubles")
+    ws = _ws(2 * n, g.device)
+    lib().call("cidnet_grad_guard", _p(g), g.numel(), _f(grad_scale), _f(0.0 if max_norm is None else max_norm),
+               int(bool(skip_nonfinite)), _f(beta1), _f(beta2), _p(loss), _p(ws), ws.numel() // 2, _p(state), _p(record),
+               _vp(log_row_ptr) if log_row_ptr else None, _stream())
+
+
+def adam_step_dev(p, g, m, v, lr, beta1, beta2, eps, weight_decay, record):
+    """cidnet_adam_step with the gradient scale, the bias corrections and the apply / skip decision read from `record`"""
+    _check(p, g, m, v, record)
+    lib().call("cidnet_adam_step_dev", _p(p), _p(g), _p(m), _p(v), p.numel(), _f(lr), _f(beta1), _f(beta2), _f(eps),
+               _f(weight_decay), _p(record), _stream())
+
+
 # --------------------------------------------------------------------------------------------
 # gradient arena: weight gradients are written straight into one flat buffer (the all-reduce /
 # optimizer operand) instead of 191 separately allocated tensors.  The op layer reads the active

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 9
+#define CIDNET_ABI_VERSION 10
 
 int cidnet_abi_version(void);
 
@@ -407,6 +407,27 @@ int cidnet_mse_loss(const float* a, const float* b, float* grad, float* loss, fl
 int cidnet_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
                      float beta2, float eps, float weight_decay, int step, float grad_scale,
                      void* stream);
+/* Guard in front of the Adam step, decided on the device (csrc/guard.hip).  g[0..n): the flat gradient after the all-reduce.
+ *   sum   = sum of g[i]^2 in fp64: per-block partials in fixed slots of ws (cidnet_grad_guard_ws_doubles() doubles), added in
+ *           a fixed order by one block in a second launch; no atomics, repeated calls are bit-identical
+ *   norm  = sqrt(sum) * grad_scale            (the 2-norm of the averaged gradient, what clip_grad_norm_ sees under DDP)
+ *   coef  = min(1, max_norm / (norm + 1e-6))  (torch's formula, norm_type = 2); 1 when max_norm <= 0 or is not finite
+ *   apply = isfinite(sum) || !skip_nonfinite  (one NaN or +-Inf element makes the sum non-finite)
+ * state  (2 int64, device, owned by the caller, zero at the start of a run): [0] steps applied, [1] steps skipped; the one
+ *        matching `apply` is incremented.
+ * record (4 fp32, device): [0] apply as 1.0 / 0.0, [1] grad_scale * coef, [2] 1 - beta1^t, [3] sqrt(1 - beta2^t) with t the
+ *        applied count after this step (powers in fp64); read by cidnet_adam_step_dev.
+ * log_row (4 fp64, device, may be NULL): [0] loss[0] (NaN when loss is NULL), [1] norm, [2] coef, [3] the applied count after
+ *        this step when it was applied, -(applied count + 1) when it was skipped (so a skipped row is strictly negative).
+ * loss: the step's scalar fp32 loss on the device, or NULL. */
+long cidnet_grad_guard_ws_doubles(void);
+int cidnet_grad_guard(const float* g, long n, float grad_scale, float max_norm, int skip_nonfinite, float beta1,
+                      float beta2, const float* loss, double* ws, long ws_doubles, long* state, float* record,
+                      double* log_row, void* stream);
+/* cidnet_adam_step with grad_scale and the two bias corrections read from a cidnet_grad_guard record; when the record's
+ * apply is 0, p, m and v are not touched. */
+int cidnet_adam_step_dev(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, const float* record, void* stream);
 
 /* ---- K13: SpatialAttention of the MSSA variant (net/CIDNet_MSSA.py:10-25) ------------------------
  * out = x * sigmoid(conv7x7([mean_c x, max_c x])), w: (1,2,7,7).  stats (B,2,H,W), amax (B,H,W int32)
