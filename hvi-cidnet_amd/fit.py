@@ -19,7 +19,8 @@ What differs from the reference's loop:
     a NaN or an Inf is skipped on the device (skip_nonfinite) instead of poisoning the weights and both Adam moments;
   * `resume=` continues a run exactly (Adam moments, step counts, schedule position); the reference's own resume
     (`start_epoch` > 0: weights only, fresh Adam, restarted warm-up, shortened cosine period) is kept as it is;
-  * left out: the per-epoch training/test.png dump, the metrics .md table (on_epoch hands the numbers to the caller), the
+  * left out: the per-epoch training/test.png dump of the step's own output (the validation's enhanced images can be written:
+    val_args=dict(save_dir=...), metrics.evaluate), the metrics .md table (on_epoch hands the numbers to the caller), the
     option parser, the cyclic scheduler variant, LPIPS (metrics.py), the folder sampling of SICE / SID / LOL-blur.
 """
 from __future__ import annotations
@@ -78,7 +79,8 @@ def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, star
     Every `snapshots` epochs rank 0 writes, into out_dir, epoch_{epoch}.pth (the model's state_dict(), what the reference
     loads with strict=True) and epoch_{epoch}.train.pt (the trainer's state_dict(), the epoch, the position in the schedule
     and the arguments that fix it); then, when val_pairs is given, metrics.evaluate(model, val_pairs, **val_args) runs and
-    the record gains psnr / ssim.
+    the record gains psnr / ssim (val_args may carry save_dir: the scored images are then also written there, each
+    validation over the last one's files).
     Record: epoch, lr, steps, skipped, loss (mean over the applied steps, see epoch_stats; averaged over the ranks with one
     all-reduce per epoch), grad_norm_max, clipped (applied steps with coef < 1).  on_epoch(record) runs on every rank.
     start_epoch > 0 is the reference's resume: the caller loads weights, Adam starts fresh, the warm-up restarts.

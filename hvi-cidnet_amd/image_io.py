@@ -1,0 +1,390 @@
+"""Image files in and out: what the reference's eval.py, eval_SID_blur.py, demo.py and app.py do around the model -- PIL image
+-> ToTensor -> reflect pad to a multiple of 8 -> ** gamma -> model -> clamp -> crop -> ToPILImage -> save under the input's
+file name -- with the image crossing the host link as 3 bytes per pixel in both directions and the model the only thing
+between two launches of this package's own kernels.
+
+    from hvi_cidnet_amd import ingest, egress, enhance_u8, enhance_folder
+    x, (h, w) = ingest(img_u8, gamma=1.0)          # uint8 (B,h,w,3) on the device -> fp32 (B,3,Hp,Wp), Hp, Wp multiples of 8
+    q = egress(model(x), (h, w))                   # fp32 (B,3,Hp,Wp) -> uint8 (B,h,w,3) on the device
+    q = enhance_u8(model, img_u8, gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0)
+    report = enhance_folder(model, in_dir, out_dir, batch_size=8, threads=16)
+
+The kernels are csrc/imageio.hip (C ABI: cidnet_image_ingest / cidnet_image_egress, semantics in include/cidnet_hip.h).
+
+enhance_folder is a pipeline; who owns what, and when:
+  * decode workers (min(threads, 16)) read one file each through PIL's .convert('RGB') and write its bytes into a pinned
+    per-image staging buffer that the main thread handed them; a buffer still too small is grown by the main thread;
+  * the main thread is the only one that talks to the device.  Per batch: one non-blocking copy of 3 h w bytes per image on
+    the upload stream, an event, the three stages of enhance_u8 on the current stream, an event, one non-blocking copy of the
+    uint8 result into a pinned output buffer on the download stream, an event.  The two copy streams carry pinned copies
+    and nothing else (concurrency rule);
+  * encode workers wait for the download's event -- in the worker, never in the main thread -- and save through PIL;
+  * at most `depth` batches are past the decode stage at any time.  A batch's staging buffers, device input and pinned output
+    go back to the pool when every encode future of that batch has completed (which implies that its upload, its kernels
+    and its download have); the main thread waits for futures only and never synchronises the device.
+"""
+from __future__ import annotations
+
+import collections
+import concurrent.futures as cf
+import os
+import threading
+import time
+from dataclasses import dataclass, field
+
+import torch
+import torch.distributed as dist
+
+from . import metrics, ops
+from ._lib import lib
+from .data import gamma_table
+
+_NO_CPU = metrics._NO_CPU
+_tables = {}                      # (device index, gamma) -> the 256-entry table on the device
+
+
+def padded_size(h, w, multiple=8):
+    """(Hp, Wp) of inference.pad_to_multiple: ((h + f) // f) * f where h % f != 0, else h"""
+    f = int(multiple)
+    if f <= 0:
+        raise ValueError(f"multiple must be positive (got {multiple})")
+    return (((h + f) // f) * f if h % f else h), (((w + f) // f) * f if w % f else w)
+
+
+def _check_reflect(h, w, Hp, Wp):
+    if Hp - h > h - 1 or Wp - w > w - 1:
+        raise ValueError(f"a {h} x {w} image cannot be reflect-padded to {Hp} x {Wp}: the pad must be smaller than the side")
+
+
+def _table_on(device, gamma):
+    gamma = float(gamma)
+    if not gamma > 0:
+        raise ValueError(f"gamma must be positive (got {gamma})")
+    if gamma == 1.0:
+        return None
+    key = (device.index if device.index is not None else torch.cuda.current_device(), gamma)
+    if key not in _tables:
+        if len(_tables) >= 64:
+            _tables.clear()
+        _tables[key] = torch.from_numpy(gamma_table(gamma)).to(device)
+    return _tables[key]
+
+
+def _images_u8(images, what):
+    """-> (B,h,w,3) uint8 whose images are dense (a batch stride >= 3 h w is kept: no copy)"""
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8:
+        raise RuntimeError(f"{what}: expected a uint8 tensor, got {getattr(images, 'dtype', type(images).__name__)}")
+    if not images.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    t = images.unsqueeze(0) if images.dim() == 3 else images
+    if t.dim() != 4 or t.shape[-1] != 3 or 0 in t.shape:
+        raise RuntimeError(f"{what}: expected (B,h,w,3) or (h,w,3), got {tuple(images.shape)}")
+    B, h, w, _ = t.shape
+    dense = t.stride()[1:] == (3 * w, 3, 1) and (B == 1 or t.stride(0) >= 3 * h * w)
+    return t if dense else t.contiguous()
+
+
+def _ingest(t, table, multiple=8):
+    B, h, w, _ = t.shape
+    Hp, Wp = padded_size(h, w, multiple)
+    _check_reflect(h, w, Hp, Wp)
+    x = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=t.device)
+    with torch.cuda.device(t.device):
+        lib().call("cidnet_image_ingest", ops._p(t), t.stride(0) if B > 1 else 3 * h * w, ops._p(table), ops._p(x), B, h, w, Hp,
+                   Wp, ops._stream())
+    return x, (h, w)
+
+
+def ingest(images_u8: torch.Tensor, gamma: float = 1.0, multiple: int = 8):
+    """uint8 (B,h,w,3) (or (h,w,3)) on the device, as PIL / numpy hold an image -> (x, (h, w)): x fp32 (B,3,Hp,Wp) =
+    pow(ToTensor(image), gamma), reflect-padded at the bottom and right to multiples of `multiple` (pad_to_multiple's
+    arithmetic), from one kernel launch.  gamma != 1 goes through data.gamma_table (fp64 power, rounded once).  ValueError for
+    gamma <= 0 and for an image too small to be reflected (pad >= side), before anything is launched."""
+    if isinstance(images_u8, torch.Tensor) and not images_u8.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    t = _images_u8(images_u8, "ingest")
+    _check_reflect(t.shape[1], t.shape[2], *padded_size(t.shape[1], t.shape[2], multiple))
+    return _ingest(t, _table_on(t.device, gamma), multiple)
+
+
+def egress(out: torch.Tensor, size=None) -> torch.Tensor:
+    """fp32 (B,3,Hp,Wp) (or (3,Hp,Wp)) on the device -> uint8 (B,h,w,3) on the device: the top-left (h, w) = `size` crop (default
+    the whole image) of trunc(clamp(x, 0, 1) * 255.0f), interleaved as PIL takes it -- value for value metrics.to_uint8
+    (eval.py:69-73 and ToPILImage).  NaN becomes 0."""
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
+        raise RuntimeError(f"egress: expected an fp32 tensor (got {getattr(out, 'dtype', type(out).__name__)})")
+    if not out.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    x = metrics._batched(out, "egress")
+    B, _, Hp, Wp = x.shape
+    h, w = (Hp, Wp) if size is None else (int(size[0]), int(size[1]))
+    if not (0 < h <= Hp and 0 < w <= Wp):
+        raise RuntimeError(f"egress: crop {(h, w)} outside the {(Hp, Wp)} image")
+    q = torch.empty((B, h, w, 3), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        lib().call("cidnet_image_egress", ops._p(x), ops._p(q), 3 * h * w, B, Hp, Wp, h, w, ops._stream())
+    return q
+
+
+def _run(model, t, table):
+    """ingest -> model -> egress of a checked (B,h,w,3) batch; the caller holds the model's state (metrics._eval_state)"""
+    x, hw = _ingest(t, table)
+    out = model(x)
+    if isinstance(out, tuple):                                   # CIDNet_TNSM: (rgb, noise map or None)
+        out = out[0]
+    return egress(out, hw)
+
+
+def _trans_attrs(gated, alpha_s, gated2, alpha):
+    return dict(gated=bool(gated), alpha_s=float(alpha_s), gated2=bool(gated2), alpha=float(alpha))
+
+
+@torch.no_grad()
+def enhance_u8(model, images_u8: torch.Tensor, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3,
+               gated2: bool = False, alpha: float = 1.0) -> torch.Tensor:
+    """uint8 (B,h,w,3) (or (h,w,3)) on the device -> the enhanced images, uint8 (B,h,w,3) on the device: ingest, the model in
+    eval mode under no_grad with trans.gated / alpha_s / gated2 / alpha set (a tuple result -- CIDNet_TNSM -- gives its [0]),
+    egress.  The model's attributes and the train / eval mode of every submodule are restored afterwards."""
+    if isinstance(images_u8, torch.Tensor) and not images_u8.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    t = _images_u8(images_u8, "enhance_u8")
+    _check_reflect(t.shape[1], t.shape[2], *padded_size(t.shape[1], t.shape[2]))
+    table = _table_on(t.device, gamma)
+    with metrics._eval_state(model, _trans_attrs(gated, alpha_s, gated2, alpha)), torch.cuda.device(t.device):
+        return _run(model, t, table)
+
+
+# ---- the batching plan (pure host code) -------------------------------------------------------------------------------
+def shard(n, rank=0, world=1):
+    """input positions of rank's images: i % world == rank, in input order"""
+    if world <= 0 or not 0 <= rank < world:
+        raise ValueError(f"rank {rank} of {world}")
+    return range(rank, n, world)
+
+
+def plan_batches(sizes, rank=0, world=1, batch_size=1):
+    """The batches of enhance_folder for one rank.  sizes: (h, w) of this rank's images -- input positions shard(n, rank,
+    world) -- in that order, consumed one at a time (a batch is yielded once the image after it has been seen).  Yields the
+    input positions of each batch: consecutive images of equal size, at most batch_size of them (metrics._plan's index
+    arithmetic with the image size standing for both the padded shape and the crop)."""
+    for _, _, runs in metrics._plan((((int(h), int(w)),) * 2 for h, w in sizes), rank, world, max(1, int(batch_size))):
+        yield [i for _, _, rows in runs for i in range(rows.start, rows.stop, rows.step)]
+
+
+# ---- the writer: device uint8 -> pinned -> files, `depth` batches deep ------------------------------------------------------
+class _Writer:
+    """put(q, paths): q uint8 (B,h,w,3) on the device, complete on the current stream when put() is called -> one
+    non-blocking copy into a pinned buffer on the download stream and one encode task per image, which waits for that copy's
+    event in its worker and saves through PIL.  At most `depth` batches are in flight: put() first retires the oldest one
+    (waits for its futures; the time goes to `waited`) when they are.  on_done() of a batch runs when it is retired.  The
+    first exception of a worker surfaces from retire() / put() / close() with the file's name."""
+
+    def __init__(self, device, threads=8, depth=2):
+        self.device, self.depth = device, max(1, int(depth))
+        self.pool = cf.ThreadPoolExecutor(max_workers=max(1, min(int(threads), 16)), thread_name_prefix="cidnet-encode")
+        self.down = torch.cuda.Stream(device)
+        self.host = [None] * self.depth                          # pinned output buffers
+        self.inflight = collections.deque()                      # (futures, on_done, q kept alive)
+        self.count = 0
+        self.waited = 0.0
+        self.stop = threading.Event()
+
+    def _save(self, event, host, k, h, w, path):
+        if self.stop.is_set():
+            return
+        try:
+            from PIL import Image
+            event.synchronize()
+            n = 3 * h * w
+            Image.fromarray(host[k * n:(k + 1) * n].view(h, w, 3).numpy()).save(path)
+        except Exception as e:
+            raise RuntimeError(f"image_io: {os.path.basename(path)}: could not be written: {e}") from e
+
+    def retire(self):
+        """wait for the oldest batch in flight; False when there is none"""
+        if not self.inflight:
+            return False
+        futures, on_done, _ = self.inflight.popleft()
+        t0 = time.perf_counter()
+        try:
+            for f in futures:
+                f.result()
+        finally:
+            self.waited += time.perf_counter() - t0
+        if on_done is not None:
+            on_done()
+        return True
+
+    def put(self, q, paths, on_done=None):
+        while len(self.inflight) >= self.depth:
+            self.retire()
+        B, h, w, _ = q.shape
+        slot = self.count % self.depth
+        self.count += 1
+        n = q.numel()
+        if self.host[slot] is None or self.host[slot].numel() < n:
+            self.host[slot] = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+        host = self.host[slot]
+        ready = torch.cuda.Event()
+        ready.record()                                           # q is complete here on the current stream
+        self.down.wait_event(ready)
+        with torch.cuda.stream(self.down):
+            host[:n].view(B, h, w, 3).copy_(q, non_blocking=True)
+        q.record_stream(self.down)
+        done = torch.cuda.Event()
+        done.record(self.down)
+        futures = [self.pool.submit(self._save, done, host, k, h, w, p) for k, p in enumerate(paths)]
+        self.inflight.append((futures, on_done, q))
+
+    def close(self):
+        try:
+            while self.retire():
+                pass
+        finally:
+            self.abort()
+
+    def abort(self):
+        """stop: queued tasks return at once, running ones finish; nothing is left running"""
+        self.stop.set()
+        self.pool.shutdown(wait=True, cancel_futures=True)
+        self.inflight.clear()
+
+
+# ---- enhance a folder -------------------------------------------------------------------------------------------------
+@dataclass
+class EnhanceReport:
+    """What one rank's enhance_folder did: names / sizes (h, w) of its images in input order, batches (the input positions of
+    each launch), seconds: {"wall": the call, "wait_for_slot": of it, the main thread waiting for a batch in flight to
+    finish so that its buffers come free}"""
+    names: list = field(default_factory=list)
+    sizes: list = field(default_factory=list)
+    batches: list = field(default_factory=list)
+    seconds: dict = field(default_factory=dict)
+
+
+class _Stage:
+    """a pinned per-image staging buffer; grown by the main thread only"""
+    __slots__ = ("buf",)
+
+    def __init__(self):
+        self.buf = None
+
+
+def _decode(stop, path, name, stage):
+    """worker: -> (h, w, None) with the bytes in the stage, or (h, w, array) when the stage is too small for them"""
+    if stop.is_set():
+        return None
+    try:
+        a = metrics._read_rgb(path)
+        h, w, _ = a.shape
+        if stage.buf is None or stage.buf.numel() < a.size:
+            return h, w, a
+        stage.buf[:a.size].view(h, w, 3).numpy()[...] = a
+        return h, w, None
+    except Exception as e:
+        raise RuntimeError(f"enhance_folder: {name}: could not be read: {e}") from e
+
+
+@torch.no_grad()
+def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
+                   alpha: float = 1.0, batch_size: int = 1, threads: int = 8, depth: int = 2, process_group=None) -> EnhanceReport:
+    """eval.py / demo.py for a folder: every image file of in_dir (metrics.folder_images: its files and order) is enhanced as
+    enhance_u8 does and saved to out_dir/<same file name> by PIL in the format its extension names (the reference's
+    output_img.save(output_folder + name[0])); out_dir is created.  Decoding, the device and encoding overlap (module
+    docstring): `threads` decode and as many encode workers (16 at most), `depth` batches in flight, consecutive images of
+    equal size sharing a batch of up to batch_size.  depth=1, threads=1 is the serial order; the files do not depend on any of
+    the three.  With a process group (or an initialised default group) rank r takes images i % world == r; no collective runs
+    and each rank reports its own images.  The first error of a worker stops the pipeline and is raised naming the file.
+    The model's attributes and modes are restored afterwards."""
+    t_start = time.perf_counter()
+    device = metrics._model_device(model)
+    if device.type != "cuda":
+        raise RuntimeError(_NO_CPU)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    files = in_dir if isinstance(in_dir, metrics.FolderImages) else metrics.folder_images(in_dir)
+    world, rank = 1, 0
+    if process_group is not None or (dist.is_available() and dist.is_initialized()):
+        world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+    batch_size, depth = max(1, int(batch_size)), max(1, int(depth))
+    workers = max(1, min(int(threads), 16))
+    mine = list(shard(len(files), rank, world))
+    report = EnhanceReport(names=[files.names[i] for i in mine])
+    os.makedirs(out_dir, exist_ok=True)
+    if not mine:
+        report.seconds = {"wall": time.perf_counter() - t_start, "wait_for_slot": 0.0}
+        return report
+
+    stop = threading.Event()
+    decoders = cf.ThreadPoolExecutor(max_workers=workers, thread_name_prefix="cidnet-decode")
+    writer = _Writer(device, workers, depth)
+    # depth batches in flight + the batch being formed + the image _plan looks ahead
+    free = [_Stage() for _ in range((depth + 1) * batch_size + 1)]
+    pending = collections.deque()                                # decodes submitted, not yet consumed: (position, stage, future)
+    loaded = []                                                  # consumed, not yet launched: (stage, h, w)
+    dev_in = [None] * depth
+    todo = iter(mine)
+
+    def submit():
+        while free:
+            i = next(todo, None)
+            if i is None:
+                return
+            stage = free.pop()
+            pending.append((i, stage, decoders.submit(_decode, stop, files.paths[i], files.names[i], stage)))
+
+    def sizes():
+        for _ in mine:
+            submit()
+            while not pending:                                   # every stage is held by a batch in flight: wait for the oldest
+                if not writer.retire():
+                    raise AssertionError("enhance_folder: no staging buffer free and no batch in flight")
+                submit()
+            _, stage, fut = pending.popleft()
+            h, w, a = fut.result()
+            if a is not None:                                    # the stage was too small: grow it here, in the main thread
+                stage.buf = torch.empty(a.size, dtype=torch.uint8, pin_memory=True)
+                stage.buf.view(h, w, 3).numpy()[...] = a
+            loaded.append((stage, h, w))
+            report.sizes.append((h, w))
+            yield h, w
+
+    try:
+        with torch.cuda.device(device), metrics._eval_state(model, _trans_attrs(gated, alpha_s, gated2, alpha)):
+            table = _table_on(device, gamma)
+            up = torch.cuda.Stream(device)
+            for n_batch, positions in enumerate(plan_batches(sizes(), rank, world, batch_size)):
+                B = len(positions)
+                batch, loaded[:B] = loaded[:B], []
+                _, h, w = batch[0]
+                try:
+                    _check_reflect(h, w, *padded_size(h, w))
+                except ValueError as e:
+                    raise ValueError(f"enhance_folder: {files.names[positions[0]]}: {e}") from None
+                while len(writer.inflight) >= depth:             # the device input of this slot belongs to a batch in flight
+                    writer.retire()
+                n, slot = 3 * h * w, n_batch % depth
+                if dev_in[slot] is None or dev_in[slot].numel() < B * n:
+                    dev_in[slot] = torch.empty(B * n, dtype=torch.uint8, device=device)
+                    up.wait_stream(torch.cuda.current_stream())  # fresh memory of the compute stream's pool
+                t = dev_in[slot][:B * n].view(B, h, w, 3)
+                with torch.cuda.stream(up):
+                    for k, (stage, _, _) in enumerate(batch):
+                        t[k].copy_(stage.buf[:n].view(h, w, 3), non_blocking=True)
+                uploaded = torch.cuda.Event()
+                uploaded.record(up)
+                torch.cuda.current_stream().wait_event(uploaded)
+                q = _run(model, t, table)
+                stages = [b[0] for b in batch]
+                writer.put(q, [os.path.join(out_dir, files.names[i]) for i in positions], on_done=lambda s=stages: free.extend(s))
+                report.batches.append(positions)
+            writer.close()
+    except BaseException:
+        stop.set()
+        writer.abort()
+        raise
+    finally:
+        stop.set()
+        decoders.shutdown(wait=True, cancel_futures=True)
+    report.seconds = {"wall": time.perf_counter() - t_start, "wait_for_slot": writer.waited}
+    return report

@@ -1,11 +1,12 @@
 """Image-quality evaluation on the device: the reference's eval.py (model -> clamped 8-bit output) and measure.py (PSNR,
-SSIM, optionally after the "GT mean" rescale) without the PNG round trip through the host.
+SSIM, optionally after the "GT mean" rescale).  The scores are formed on the device from the quantized output; save_dir=
+also writes the files eval.py writes (image_io's egress kernel and writer), which a PNG reader decodes to the scored values.
 
     from hvi_cidnet_amd import metrics as M
     q = M.to_uint8(rgb, size=(h, w))        # fp32 (B,3,Hp,Wp) -> uint8 (B,3,h,w): clamp, x255, truncate, crop
     p = M.psnr(q, gt_u8, gt_mean=False)     # (B,) float64 on the device, no host synchronisation
     s = M.ssim(q, gt_u8, gt_mean=False)     # (B,) float64 on the device
-    res = M.evaluate(model, pairs, gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0, batch_size=1)
+    res = M.evaluate(model, pairs, gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0, batch_size=1, save_dir=None)
     pairs = M.folder_pairs(low_dir, high_dir)
 
 and, for the sets without ground truth (eval.py --unpaired + measure_niqe_bris.py), NIQE:
@@ -13,7 +14,7 @@ and, for the sets without ground truth (eval.py --unpaired + measure_niqe_bris.p
     prm = M.load_niqe_params(path)          # the reference's loss/niqe_pris_params.npz (not shipped: pass its path)
     f = M.niqe_features(q, prm)             # uint8 (B,3,h,w) -> (B, blocks, 36) float64 on the device
     s = M.niqe(q, prm)                      # (B,) float64 (the 36 x 36 tail runs on the host: one copy per batch)
-    res = M.evaluate_unpaired(model, images, prm, alpha=1.0, gamma=1.0, batch_size=1)
+    res = M.evaluate_unpaired(model, images, prm, alpha=1.0, gamma=1.0, batch_size=1, save_dir=None)
     images = M.folder_images(dir)
 
 The kernels are csrc/metrics.hip and csrc/niqe.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
@@ -27,11 +28,13 @@ Differences from the reference scripts, none of which changes a per-image value:
   * LPIPS is not computed (it needs AlexNet weights and the lpips package's heads);
   * NIQE: the half-size image sums its 8 taps in fp64 and rounds once per pass where the reference sums them in fp32 (two
     fp32 ulps apart at most), and the block moments are summed in fp64 where the reference's are fp32 means; an image with
-    fewer than two NaN-free blocks scores NaN (the reference raises from inside the SVD); BRISQUE and the JPEG round trip
-    that eval.py's output files go through for .jpg inputs are not reproduced.
+    fewer than two NaN-free blocks scores NaN (the reference raises from inside the SVD); BRISQUE is not computed, and the
+    score is that of the quantized output itself: for a .jpg input eval.py's output file is a JPEG, and the reference scores
+    what that file decodes to (save_dir= writes the same file; its lossy round trip is not in the score).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import warnings
@@ -190,6 +193,28 @@ def _model_device(model):
     raise RuntimeError("evaluate: the model has no parameters")
 
 
+@contextlib.contextmanager
+def _eval_state(model, trans_attrs):
+    """The model as an evaluation runs it -- eval mode, the given model.trans attributes set -- and afterwards as it was found:
+    trans.gated / alpha_s / gated2 / alpha, the snapshot behind trans.this_k and the train / eval mode of every submodule.
+    Shared by _evaluate() and image_io (enhance_u8, enhance_folder).  Yields model.trans."""
+    trans = model.trans
+    saved_attrs = {k: getattr(trans, k) for k in ("gated", "alpha_s", "gated2", "alpha")}
+    saved_k = {k: trans.__dict__[k] for k in ("_this_k_host", "_this_k_dev") if k in trans.__dict__}
+    saved_modes = [(m, m.training) for m in model.modules()]
+    try:
+        model.eval()
+        for k, v in trans_attrs.items():
+            setattr(trans, k, v)
+        yield trans
+    finally:
+        for k, v in saved_attrs.items():
+            setattr(trans, k, v)
+        trans.__dict__.update(saved_k)
+        for m, mode in saved_modes:
+            m.training = mode
+
+
 def _plan(sizes, rank, world, batch_size):
     """The index arithmetic of an evaluation, free of tensors.  `sizes`: (padded shape, crop size) of this rank's images --
     images rank, rank + world, ... of the input, in that order --, consumed one at a time.  Yields (lo, hi, runs) per batch:
@@ -220,11 +245,13 @@ def _plan(sizes, rank, world, batch_size):
 
 
 @torch.no_grad()
-def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, alpha, gamma, batch_size, process_group):
+def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, alpha, gamma, batch_size, process_group,
+              save_dir=None):
     """The evaluation loop of evaluate() and evaluate_unpaired(), `who` / `noun` naming them in errors.  load(i, item, device)
     -> (input fp32 (3,h,w), what score needs of the image); trans_attrs: the model.trans attributes set for the run; score(q
     uint8 (B,3,h,w), [load's second values]) -> one (B,) fp64 device tensor per key; result(alpha=, per_image=, names=,
-    <key>=mean ...) builds the result for one alpha."""
+    <key>=mean ...) builds the result for one alpha.  save_dir: every scored image is also written there (image_io's egress
+    kernel and writer), under items.names[i] or "<i as 5 digits>.png"."""
     device = _model_device(model)
     if not device.type == "cuda":
         raise RuntimeError(_NO_CPU)
@@ -232,6 +259,8 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
     alphas = [float(a) for a in alpha] if sweep else [float(alpha)]
     if not alphas:
         raise ValueError(f"{who}: empty alpha sweep")
+    if sweep and save_dir is not None:
+        raise ValueError(f"{who}: save_dir with an alpha sweep -- the files of which alpha? Evaluate one alpha per directory")
     n = len(items)
     if n == 0:
         raise ValueError(f"{who}: no {noun}")
@@ -239,13 +268,16 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
     if process_group is not None or (dist.is_available() and dist.is_initialized()):
         world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
     use_trunk = sweep and hasattr(model, "trunk")
-    trans = model.trans
-    saved_attrs = {k: getattr(trans, k) for k in ("gated", "alpha_s", "gated2", "alpha")}
-    saved_k = {k: trans.__dict__[k] for k in ("_this_k_host", "_this_k_dev") if k in trans.__dict__}
-    saved_modes = [(m, m.training) for m in model.modules()]
     # rows: images in input order; columns: keys.  This rank fills the rows of its images, zeros elsewhere.
     res = torch.zeros((len(alphas), n, len(keys)), dtype=torch.float64, device=device)
     loaded = []                # this rank's images not yet scored: (padded input, (h, w), load's second); _plan looks one ahead
+    writer = None
+    if save_dir is not None:
+        from . import image_io                                   # image_io imports this module
+        os.makedirs(save_dir, exist_ok=True)
+        file_names = getattr(items, "names", None)
+        with torch.cuda.device(device):
+            writer = image_io._Writer(device, threads=8, depth=2)
 
     def sizes():
         for i in range(rank, n, world):
@@ -254,10 +286,7 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
             loaded.append((xp, hw, aux))
             yield xp.shape, hw
     try:
-        model.eval()
-        for k, v in trans_attrs.items():
-            setattr(trans, k, v)
-        with torch.cuda.device(device):
+        with _eval_state(model, trans_attrs) as trans, torch.cuda.device(device):
             for lo, hi, runs in _plan(sizes(), rank, world, max(1, int(batch_size))):
                 batch = loaded[:hi - lo]
                 del loaded[:hi - lo]
@@ -277,15 +306,20 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
                         into = res[ai, rows]
                         for col, v in enumerate(score(q, [b[2] for b in batch[j:k]])):
                             into[:, col].copy_(v)
-        if world > 1:
-            dist.all_reduce(res, op=dist.ReduceOp.SUM, group=process_group)
-        host = res.cpu().numpy()
+                        if writer is not None:
+                            ids = range(rows.start, rows.stop, rows.step)
+                            writer.put(image_io.egress(out[j:k], batch[j][1]),
+                                       [os.path.join(save_dir, str(file_names[i]) if file_names is not None else f"{i:05d}.png")
+                                        for i in ids])
+            if writer is not None:
+                writer.close()
+                writer = None
+            if world > 1:
+                dist.all_reduce(res, op=dist.ReduceOp.SUM, group=process_group)
+            host = res.cpu().numpy()
     finally:
-        for k, v in saved_attrs.items():
-            setattr(trans, k, v)
-        trans.__dict__.update(saved_k)
-        for m, mode in saved_modes:
-            m.training = mode
+        if writer is not None:
+            writer.abort()
     names = list(getattr(items, "names", range(n)))
     out = []
     for ai, a in enumerate(alphas):
@@ -301,7 +335,7 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
 
 
 def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
-             alpha=1.0, batch_size: int = 1, process_group=None):
+             alpha=1.0, batch_size: int = 1, process_group=None, save_dir=None):
     """eval.py + measure.py on the device.  `pairs`: a sequence of (low, gt) -- low a (3,h,w) float image in [0, 1] (or a
     uint8 HWC image, converted as ToTensor() does), gt uint8 HWC / CHW or a float ToTensor() image of the same size
     (folder_pairs() yields these).  Each input is reflect-padded to a multiple of 8, run through model(pow(x, gamma)) in eval
@@ -314,6 +348,9 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     Data-parallel: with torch.distributed initialised (or `process_group` given), rank r evaluates images i % world == r and
     the per-image values are gathered back into image order with one SUM all-reduce, so every rank returns the same result
     (with batch_size=1 bit-identical to a single process).
+    save_dir: each scored image is also written to save_dir/<name> (pairs.names[i] where the pairs have names, else
+    "<i as 5 digits>.png") by PIL in the format the name's extension gives -- the files eval.py writes and measure.py reads;
+    each rank writes its own images.  ValueError together with an alpha sweep.  None: nothing is written.
     The model's attributes and the train / eval mode of every submodule are restored afterwards."""
     def load(i, pair, device):
         x, g = _image_f32(pair[0], device), _gt_u8(pair[1], device)
@@ -328,7 +365,7 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     skipped = list(getattr(pairs, "skipped", []))
     return _evaluate("evaluate", "image pairs", model, pairs, load,
                      dict(gated=bool(gated), alpha_s=float(alpha_s), gated2=bool(gated2)), score, _KEYS,
-                     lambda **kw: EvalResult(skipped=skipped, **kw), alpha, gamma, batch_size, process_group)
+                     lambda **kw: EvalResult(skipped=skipped, **kw), alpha, gamma, batch_size, process_group, save_dir)
 
 
 # ---- folder pairing (the one piece of host / disk code) ------------------------------------------------------------
@@ -596,7 +633,8 @@ class UnpairedResult:
     names: list = field(default_factory=list)
 
 
-def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batch_size: int = 1, process_group=None):
+def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batch_size: int = 1, process_group=None,
+                      save_dir=None):
     """eval.py --unpaired + measure_niqe_bris.py on the device.  `images`: a sequence of (3,h,w) float images in [0, 1] (or
     uint8 HWC images, converted as ToTensor() does; folder_images() yields these), each at least 96 x 96.  Each is reflect-
     padded to a multiple of 8, run through model(pow(x, gamma)) in eval mode under no_grad with trans.gated2 = True and
@@ -606,8 +644,9 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
     alpha: a number, or a sequence (a sweep): the result is then a list with one UnpairedResult per value and the model's
     trunk runs once per batch, as in evaluate().  batch_size > 1 batches consecutive images of equal padded size.
     Data-parallel as evaluate(): rank r scores images i % world == r, one SUM all-reduce gathers the values.
+    save_dir: as evaluate() -- the enhanced images are also written there, under images.names[i] or "<i as 5 digits>.png".
     The model's attributes and the train / eval mode of every submodule are restored afterwards.
-    Not reproduced: the JPEG round trip of eval.py's outputs for .jpg inputs, and BRISQUE."""
+    Not reproduced: BRISQUE; and the score is the quantized output's, not that of a lossy file decoded again (.jpg names)."""
     prm = _niqe_params(params)
 
     def load(i, img, device):
@@ -617,7 +656,7 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
                              f"{NIQE_BLOCK} x {NIQE_BLOCK} pixels")
         return x, None
     return _evaluate("evaluate_unpaired", "images", model, images, load, dict(gated2=True), lambda q, _: (niqe(q, prm),),
-                     ("niqe",), UnpairedResult, alpha, gamma, batch_size, process_group)
+                     ("niqe",), UnpairedResult, alpha, gamma, batch_size, process_group, save_dir)
 
 
 class FolderImages:

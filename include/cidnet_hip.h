@@ -11,7 +11,8 @@
  *   - all tensors are fp32, NCHW-contiguous device memory unless a stride argument says otherwise;
  *     "HW" planes are H*W floats; pointers are plain device pointers owned by the caller;  the one
  *     exception are the evaluation metrics (cidnet_metric_*), whose images are uint8 (B,3,h,w) and
- *     whose results are fp64 device buffers, and the training-batch kernel (cidnet_augment_*), which reads a uint8 arena;
+ *     whose results are fp64 device buffers, the training-batch kernel (cidnet_augment_*), which reads a uint8 arena, and
+ *     the image ingest / egress kernels (cidnet_image_*), whose byte side is interleaved (h,w,3) uint8;
  *   - `stream` is a hipStream_t passed as void* (the caller's current stream; NULL = default);
  *   - functions are stateless and re-entrant, never allocate, never synchronise and never copy to
  *     the host, so a caller may capture them into a hipGraph;  scratch memory comes in through
@@ -28,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 10
+#define CIDNET_ABI_VERSION 11
 
 int cidnet_abi_version(void);
 
@@ -560,6 +561,27 @@ int cidnet_metric_niqe_features(const uint8_t* rgb, const double* window, const 
  * and independent of the rest of the batch. */
 int cidnet_augment_crop_flip(const uint8_t* arena, const long* plan, const float* table, float* x, float* gt, int B, int Sh,
                              int Sw, void* stream);
+
+/* ---- Image files in and out (eval.py:60-75, eval_SID_blur.py, demo.py:40-60, app.py:33-53 of the reference: PIL image ->
+ * ToTensor -> reflect pad to a multiple of 8 -> ** gamma -> model -> clamp -> crop -> ToPILImage -> save): the two conversions
+ * between the interleaved (h,w,3) uint8 bytes of PIL / numpy / every file format and the planar fp32 (B,3,Hp,Wp) tensor of the
+ * model, so that an image crosses the host link as 3 bytes per pixel in both directions.  The byte side holds B images, image
+ * b at base + b * bs bytes (src_bs / dst_bs >= 3 h w; any byte alignment of base and bs); the fp32 side is contiguous.
+ * ingest: for i < Hp, j < Wp, with ri = i < h ? i : 2(h-1) - i and rj = j < w ? j : 2(w-1) - j (F.pad(..., 'reflect') at the
+ *   bottom and right: eval_sets.py:22-28, demo.py:47-52, app.py:35-40):  x[b,c,i,j] = T[src_b[ri,rj,c]].  table: 256 fp32
+ *   values on the device, pow(q / 255, gamma) per level as the caller rounded it (hvi-cidnet_amd/data.py: gamma_table); table
+ *   == NULL: T[q] = fp32(q) / 255.0f, a correctly rounded division (ToTensor).  Hp < h, Wp < w, Hp - h > h - 1 or Wp - w > w - 1
+ *   is CIDNET_ERR_SHAPE (a reflection needs the pad to be smaller than the side); Hp and Wp need not be multiples of anything.
+ * egress: for i < h, j < w:  dst_b[i,j,c] = (uint8) trunc(clamp(x[b,c,i,j], 0, 1) * 255.0f), NaN -> 0 (eval.py:69-73 with
+ *   ToPILImage's pic.mul(255).byte()): value for value what cidnet_metric_to_uint8 writes, interleaved.  h > Hp or w > Wp is
+ *   CIDNET_ERR_SHAPE.  Exactly the 3 h w bytes of each image are written: not one byte of the slack between images or after
+ *   the last one is touched.
+ * Both: only the 3 h w bytes of an image are ever read on the byte side.  bs < 3 h w, B > 65535 or more than 2^30 groups of
+ * four pixels per image is CIDNET_ERR_SHAPE.  No atomics, no reductions: a value depends on its own image alone, bit-identical
+ * from call to call and independent of the rest of the batch. */
+int cidnet_image_ingest(const uint8_t* src, long src_bs, const float* table, float* x, int B, int h, int w, int Hp, int Wp,
+                        void* stream);
+int cidnet_image_egress(const float* x, uint8_t* dst, long dst_bs, int B, int Hp, int Wp, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,61 @@
+"""Enhance a file or a folder: the reference's demo.py and eval.py in one script.  Every image file of --input (or the one
+file) goes through hvi_cidnet_amd.enhance_folder -- decode, upload as bytes, ingest kernel, model, egress kernel, download as
+bytes, encode, pipelined -- and is saved to --output_dir under its own name.  Prints one JSON line built from the report.
+
+    python tools/enhance.py --input datasets/LOLdataset/eval15/low --output_dir output/LOLv1 --weight weights/LOLv1/w_perc.pth
+    python tools/enhance.py --input photo.jpg --output_dir out --weight weights/generalization.safetensors --gamma 0.8 --alpha_s 1.1
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+VARIANTS = {"base": "CIDNet", "mssa": "CIDNet_MSSA", "tnsm": "CIDNet_TNSM"}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--input", required=True, help="an image file, or a directory of image files")
+    ap.add_argument("--output_dir", required=True)
+    ap.add_argument("--weight", required=True, help=".pth state_dict, .safetensors, or a directory holding model.safetensors")
+    ap.add_argument("--variant", choices=sorted(VARIANTS), default="base")
+    ap.add_argument("--gamma", type=float, default=1.0)
+    ap.add_argument("--alpha_s", type=float, default=1.3)
+    ap.add_argument("--alpha_i", type=float, default=1.0)
+    ap.add_argument("--gated", action="store_true")
+    ap.add_argument("--gated2", action="store_true")
+    ap.add_argument("--batch_size", type=int, default=1)
+    ap.add_argument("--threads", type=int, default=8)
+    ap.add_argument("--depth", type=int, default=2)
+    a = ap.parse_args(argv)
+    if not os.path.exists(a.input):
+        ap.error(f"--input {a.input}: no such file or directory")
+
+    import torch
+    import hvi_cidnet_amd as P
+    from hvi_cidnet_amd import metrics as M
+    if not torch.cuda.is_available():
+        sys.exit("tools/enhance.py needs a ROCm device: the package has no CPU path")
+    model = getattr(P, VARIANTS[a.variant])()
+    missing, unexpected = P.load_weights(model, a.weight)
+    model = model.to("cuda:0").eval()
+    if os.path.isdir(a.input):
+        files = M.folder_images(a.input)
+    else:                                                        # a single file goes through the same driver
+        files = M.FolderImages([a.input], [os.path.basename(a.input)])
+    if len(files) == 0:
+        sys.exit(f"no image file (.png .jpg .bmp .JPG .jpeg) in {a.input}")
+    rep = P.enhance_folder(model, files, a.output_dir, gamma=a.gamma, gated=a.gated, alpha_s=a.alpha_s, gated2=a.gated2,
+                           alpha=a.alpha_i, batch_size=a.batch_size, threads=a.threads, depth=a.depth)
+    wall = rep.seconds["wall"]
+    print(json.dumps({"what": "enhance", "input": a.input, "output_dir": a.output_dir, "variant": a.variant, "images": len(rep.names),
+                      "batches": len(rep.batches), "seconds": rep.seconds, "images_per_s": len(rep.names) / wall if wall > 0 else None,
+                      "missing_keys": missing, "unexpected_keys": unexpected, "names": rep.names,
+                      "sizes": [list(s) for s in rep.sizes]}))
+
+
+if __name__ == "__main__":
+    main()
