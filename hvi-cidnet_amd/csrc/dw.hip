@@ -591,6 +591,21 @@ int cidnet_iel_gate_dw_bwd_t(const void* u, const float* w1, const float* w2, co
 void cidnet_debug_dw_rows(int rows) { g_dw_force_rows = rows; }
 #endif
 
+/* the tiling a kernel family takes, from the same functions the launchers below call; launches nothing */
+int cidnet_dw_tiling(int family, long planes, int H, int W, int* rows, int* nstrips, int* chunks) {
+  CIDNET_CHECK_ARG(family >= 0 && family <= 3 && planes > 0 && H > 0 && W > 0 && rows && nstrips && chunks);
+  Tiling tl;
+  int nchunk = 1;
+  switch (family) {
+    case 0: tl = fwd_tiling(planes, H, W); break;
+    case 1: tl = dw_gate_tiling(planes, H, W); break;
+    case 2: tl = wgrad_tiling(planes, H, W); nchunk = (chunks_of(tl) + kSub - 1) / kSub; break;
+    default: tl = gate_bwd_tiling(planes, H, W); nchunk = (chunks_of(tl) + kSub - 1) / kSub; break;
+  }
+  *rows = tl.rows; *nstrips = tl.nstrips; *chunks = nchunk;
+  return CIDNET_OK;
+}
+
 int cidnet_dw3x3(const float* in, const float* w1, const float* w2, int csplit, const float* addend, float* out, int flip,
                  int B, int C, int H, int W, void* stream) {
   return cidnet_dw3x3_t(in, w1, w2, csplit, addend, out, CIDNET_F32, flip, B, C, H, W, stream);

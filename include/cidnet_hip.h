@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 11
+#define CIDNET_ABI_VERSION 12
 
 int cidnet_abi_version(void);
 
@@ -205,6 +205,13 @@ int cidnet_pw_wgrad(const float* dY, long dy_bs, const float* X, long x_bs, floa
 /* timing-study switch: force the strip height of the depthwise / gate kernels (0 = automatic) */
 void cidnet_debug_dw_rows(int rows);
 #endif
+/* the strip tiling a dw.hip kernel family takes for this problem; launches nothing.
+ * family: 0 forward (dw3x3, iel_gate_fwd/bwd), 1 iel_dw_gate_fwd, 2 dw3x3_wgrad / dw3x3_bwd, 3 iel_gate_dw_bwd.
+ * planes is B*C (families 0, 2) or B*h (1, 3).  A lane owns `rows` rows of a 4-pixel column; nstrips = ceil(H / rows).
+ * chunks = blocks per plane of the fused backward kernels (1 for families 0 and 1; cidnet_dw3x3_wgrad alone, which
+ * reduces once per 256 items, launches four times as many).  The tests assert through it that a shape reaches the
+ * strip height / chunk count it is there for. */
+int cidnet_dw_tiling(int family, long planes, int H, int W, int* rows, int* nstrips, int* chunks);
 int cidnet_dw3x3(const float* in, const float* w1, const float* w2, int csplit, const float* addend,
                  float* out, int flip, int B, int C, int H, int W, void* stream);
 /* in / addend / out stored as fp32 or bf16 (one type, dt): the CAB's q / kv depthwise convs in the bf16 mode */

@@ -27,6 +27,46 @@ def test_shipped_library_has_no_debug_state():
     assert not any(n.startswith("cidnet_debug") for n in _lib.parse_header())
 
 
+def test_dw_tiling_query_contract():
+    """cidnet_dw_tiling (host only, launches nothing): the strips cover H exactly once, heights stay inside 4..24 (or H
+    itself below 4), strips taller than 8 rows are taken only while the launch keeps the family's lane count, and bad
+    arguments are the library's argument error"""
+    from hvi_cidnet_amd import _lib
+    q = _lib.lib().raw("cidnet_dw_tiling")
+    min_lanes = (917504, 524288, 655360, 262144)
+
+    def tiling(family, planes, H, W):
+        r, n, c = ctypes.c_int(-7), ctypes.c_int(-7), ctypes.c_int(-7)
+        assert q(family, planes, H, W, ctypes.byref(r), ctypes.byref(n), ctypes.byref(c)) == 0
+        return r.value, n.value, c.value
+
+    tall = set()
+    for family in range(4):
+        for planes in (1, 2, 190, 760, 1520, 4370, 13108, 45876):
+            for H in (1, 2, 3, 4, 5, 7, 8, 9, 23, 24, 25, 49, 68, 100, 400):
+                for W in (1, 3, 7, 8, 9, 37, 150, 600):
+                    rows, nstrips, chunks = tiling(family, planes, H, W)
+                    assert rows * nstrips >= H > rows * (nstrips - 1), (family, planes, H, W, rows, nstrips)
+                    assert 4 <= rows <= 24 or (H < 4 and rows == H), (family, planes, H, W, rows)
+                    nx4 = (W + 3) // 4
+                    if planes * nstrips * nx4 < min_lanes[family]:
+                        assert rows <= 8, (family, planes, H, W, rows)
+                    if rows > 8:
+                        tall.add(family)
+                    items = nstrips * nx4
+                    assert chunks == (1 if family < 2 else max(1, -(-items // 1024))), (family, planes, H, W, chunks)
+    assert tall == {0, 1, 2, 3}                                   # the sweep does reach the tall strips of every family
+    assert tiling(3, 8 * 95, 400, 600) == (24, 17, 3)             # the training shape: a ragged last strip of 16 rows
+    r, n, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    ok = (ctypes.byref(r), ctypes.byref(n), ctypes.byref(c))
+    for bad in ((-1, 4, 8, 8), (4, 4, 8, 8), (0, 0, 8, 8), (0, -3, 8, 8), (1, 4, 0, 8), (2, 4, 8, 0), (3, 4, -1, 8)):
+        assert q(*bad, *ok) == -1, bad
+    for i in range(3):
+        ptrs = list(ok)
+        ptrs[i] = None
+        assert q(0, 4, 8, 8, *ptrs) == -1
+
+
 def test_product_path_refuses_cpu_tensors():
     import torch
     from hvi_cidnet_amd.hvi_transform import RGB_HVI
