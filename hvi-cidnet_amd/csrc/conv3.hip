@@ -21,6 +21,8 @@
 #include <type_traits>
 #include "common.h"
 #include "conv3_thin.h"
+#include "conv3_tiling.h"
+#include "cidnet_hip.h"
 
 namespace cidnet {
 namespace {
@@ -437,19 +439,31 @@ __global__ __launch_bounds__(kThreads) void conv3_kernel(C3Args a) {
 #endif
 }
 
+// Blocks of a launch with tiles 4 << logx pixels wide (every tile is 512 pixels) and tpb row tiles per block
+struct C3Grid {
+  int xt, ntiles, gy;   // tiles across, row tiles, blocks down = ceil(ntiles / tpb)
+};
+
+inline C3Grid c3_grid(int logx, int tpb, int H, int W) {
+  const int xl4 = 4 << logx, trows = 4 * (16 >> logx) * kR;
+  C3Grid g;
+  g.xt = (W + xl4 - 1) / xl4;
+  g.ntiles = (H + trows - 1) / trows;
+  g.gy = (g.ntiles + tpb - 1) / tpb;
+  return g;
+}
+
 template <int MT, int LEFT, int LOGX, bool NARROW>
 int launch_c3x(C3Args a, int B, hipStream_t s) {
   constexpr int MB = 16 * MT + 4 * LEFT;
-  constexpr int XL = 1 << LOGX, NY = 16 >> LOGX;
   const int kc = ((a.K < kKC ? a.K : kKC) + 3) & ~3;
   const size_t lds = (size_t)c3_lds_floats(MB, kc) * sizeof(float);
-  const int xt = (a.W + XL * 4 - 1) / (XL * 4);
-  const int ntiles = (a.H + 4 * NY * kR - 1) / (4 * NY * kR);
-  long tpb = a.tpb > 0 ? a.tpb : 1;             // chosen together with LOGX by launch_c3's cost model
+  long tpb = a.tpb > 0 ? a.tpb : 1;             // chosen together with LOGX by c3_pick_tile's cost model
   if (a.K > kKC) tpb = 1;                        // the panel is re-staged per tile anyway
   if (((g_c3_dbg >> 8) & 0xFF) && a.K <= kKC) tpb = (g_c3_dbg >> 8) & 0xFF;     // timing study: forced tiles per block
   a.tpb = (int)tpb;
-  dim3 grid((unsigned)xt, (unsigned)((ntiles + tpb - 1) / tpb), (unsigned)(B * a.nmb));
+  const C3Grid cg = c3_grid(LOGX, a.tpb, a.H, a.W);
+  dim3 grid((unsigned)cg.xt, (unsigned)cg.gy, (unsigned)(B * a.nmb));
   if (a.R)
     hipLaunchKernelGGL((conv3_kernel<MT, LEFT, LOGX, NARROW, true>), grid, dim3(kThreads), lds, s, a);
   else
@@ -458,24 +472,26 @@ int launch_c3x(C3Args a, int B, hipStream_t s) {
   return CIDNET_OK;
 }
 
-template <int MT, int LEFT>
-int launch_c3(const C3Args& a0, int B, hipStream_t s) {
+struct C3Tile {
+  int logx, tpb, narrow;
+};
+
+inline C3Tile c3_pick_tile(int B, int nmb, int K, int H, int W) {
   // Tile shape (64 / 32 / 16 pixels wide; every tile is 512 pixels) and row tiles per block, by a cost model in units of
   // one tile's time.  The blocks of a launch run in lockstep rounds of the 512 resident blocks (2 per CU), so
   //   cost = rounds * (stage + tiles per block),  rounds = ceil(blocks / 512),  stage ~ 0.15 (tools/c3_phases.py);
   // a grid of 1064 blocks (36->36 at 200x300 with 16-pixel-wide tiles) pays three rounds for two rounds of work.
   // Ties go to the shape with less padded work, then to fewer tiles per block.
-  C3Args a = a0;
   int best = 4, best_tpb = 1;
   double best_cost = 1e30;
   long best_work = 1L << 60;
   for (int lx = 4; lx >= 2; --lx) {
-    const int xl4 = 4 << lx, trows = 4 * (16 >> lx) * kR;
-    const long xt = (a.W + xl4 - 1) / xl4, nt = (a.H + trows - 1) / trows;
-    for (int tpb = 1; tpb <= (a.K <= kKC ? 4 : 1); ++tpb) {
-      const long blocks = xt * ((nt + tpb - 1) / tpb) * B * a.nmb;
+    for (int tpb = 1; tpb <= (K <= kKC ? 4 : 1); ++tpb) {
+      const C3Grid cg = c3_grid(lx, tpb, H, W);
+      const long xt = cg.xt, nt = cg.ntiles;
+      const long blocks = xt * cg.gy * B * nmb;
       const long rounds = (blocks + 511) / 512;
-      const double stage = a.K <= kKC ? 0.15 : 0.0;          // deeper layers stage inside every tile: same for all shapes
+      const double stage = K <= kKC ? 0.15 : 0.0;            // deeper layers stage inside every tile: same for all shapes
       const double cost = (double)rounds * (stage + tpb);
       const long work = xt * nt;
       if (cost < best_cost - 1e-9 || (cost < best_cost + 1e-9 && work < best_work)) {
@@ -483,10 +499,21 @@ int launch_c3(const C3Args& a0, int B, hipStream_t s) {
       }
     }
   }
-  a.tpb = best_tpb;
-  if (a.W < 8) return launch_c3x<MT, LEFT, 2, true>(a, B, s);
-  if (best == 4) return launch_c3x<MT, LEFT, 4, false>(a, B, s);
-  if (best == 3) return launch_c3x<MT, LEFT, 3, false>(a, B, s);
+  C3Tile t;
+  t.narrow = W < 8;                              // per-element border path: its own instantiation, 16-pixel-wide tiles
+  t.logx = t.narrow ? 2 : best;
+  t.tpb = best_tpb;
+  return t;
+}
+
+template <int MT, int LEFT>
+int launch_c3(const C3Args& a0, int B, hipStream_t s) {
+  C3Args a = a0;
+  const C3Tile t = c3_pick_tile(B, a.nmb, a.K, a.H, a.W);
+  a.tpb = t.tpb;
+  if (t.narrow) return launch_c3x<MT, LEFT, 2, true>(a, B, s);
+  if (t.logx == 4) return launch_c3x<MT, LEFT, 4, false>(a, B, s);
+  if (t.logx == 3) return launch_c3x<MT, LEFT, 3, false>(a, B, s);
   return launch_c3x<MT, LEFT, 2, false>(a, B, s);
 }
 
@@ -800,6 +827,13 @@ inline WgSplit wg_split(int M, int N) {
   return w;
 }
 
+// pixel chunks (blocks along x of the grid) for rr rows per chunk: four (column tile, row chunk) items per block
+inline int wg_chunks(int H, int W, int rr, int* nitems) {
+  const int ncol = (W + 31) / 32;
+  *nitems = ncol * ((H + rr - 1) / rr);
+  return (*nitems + 3) / 4;
+}
+
 // Rows per pixel chunk.  256 CUs hold 512 of these blocks at a time (2 waves per SIMD), and a block's run time is
 // (rows + ~6 rows' worth of prologue / 9-round epilogue), so the launch costs about ceil(blocks / 512) * (rows + 6):
 // a grid just above a multiple of 512 pays a whole extra round for a few blocks.  Pick the cheapest row count >= 8.
@@ -808,14 +842,14 @@ inline WgSplit wg_split(int M, int N) {
 #endif
 inline int wg_rows(int B, int M, int N, int H, int W) {
   const WgSplit w = wg_split(M, N);
-  const int ncol = (W + 31) / 32;
   const long per_chunk = (long)w.nmb * w.nfull * B;                               // blocks of the main launch per pixel chunk
   int best_rr = H;
   long best_cost = -1;
   for (int nrc = 1; nrc <= H; ++nrc) {
     const int rr = (H + nrc - 1) / nrc;
     if (rr < 8 && nrc > 1) break;
-    const long chunks = ((long)ncol * ((H + rr - 1) / rr) + 3) / 4;
+    int nitems;
+    const long chunks = wg_chunks(H, W, rr, &nitems);
     const long rounds = (per_chunk * chunks + 511) / 512;
     const long cost = rounds * (rr + C3_WG_OVH);
     if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_rr = rr; }
@@ -897,11 +931,9 @@ int cidnet_conv3x3_add(const float* X, long x_bs, const float* Wt, long w_ms, lo
     return c3_thin_conv(X, x_bs, Wt, w_ms, w_ks, flip, replicate, Y, y_bs, B, M, K, H, W, (hipStream_t)stream);
   // split M into equal blocks of at most 48 rows; a block is MT 16-row tiles plus LEFT 4-row groups
   // (MT + LEFT <= 3 accumulator sets), e.g. 36 = 2 tiles + 1 group, 72 = 2 x 36, 144 = 3 x 48, 24 = 1 tile + 2 groups
-  const int nblk = (M + 47) / 48;
-  const int rows = (((M + nblk - 1) / nblk) + 3) & ~3;
-  int MT = rows / 16, LEFT = (rows % 16) / 4;
-  if (MT == 0 || MT + LEFT > 3 || (g_c3_dbg & 16)) { MT = (rows + 15) / 16; LEFT = 0; }
-  a.nmb = (M + 16 * MT + 4 * LEFT - 1) / (16 * MT + 4 * LEFT);
+  const WgSplit sp = wg_split(M, K);
+  const int MT = sp.MT, LEFT = sp.LEFT;
+  a.nmb = sp.nmb;
   hipStream_t s = (hipStream_t)stream;
   switch (MT * 4 + LEFT) {
     case 4: return launch_c3<1, 0>(a, B, s);
@@ -920,8 +952,8 @@ int cidnet_conv3x3(const float* X, long x_bs, const float* Wt, long w_ms, long w
 
 long cidnet_conv3x3_wgrad_ws_floats(int B, int M, int N, int H, int W) {
   if (c3_thin_applies(M, N) && !(g_c3_dbg & 8)) return (long)B * c3_thin_wgrad_chunks(H, W) * M * N * 9;
-  const int rr = wg_rows(B, M, N, H, W);
-  const long chunks = ((long)((W + 31) / 32) * ((H + rr - 1) / rr) + 3) / 4;
+  int nitems;
+  const long chunks = wg_chunks(H, W, wg_rows(B, M, N, H, W), &nitems);
   return (long)B * chunks * M * N * 9;
 }
 
@@ -948,8 +980,7 @@ int cidnet_conv3x3_wgrad(const float* dY, long dy_bs, const float* X, long x_bs,
   a.dY = dY; a.dy_bs = dy_bs; a.X = X; a.x_bs = x_bs; a.slabs = ws; a.M = M; a.N = N; a.H = H; a.W = W;
   a.replicate = replicate; a.rr = wg_rows(B, M, N, H, W);
   a.ncol = (W + 31) / 32;
-  a.nitems = a.ncol * ((H + a.rr - 1) / a.rr);
-  const int chunks = (a.nitems + 3) / 4;
+  const int chunks = wg_chunks(H, W, a.rr, &a.nitems);
   const WgSplit sp = wg_split(M, N);
   const int MT = sp.MT, LEFT = sp.LEFT, nmb = sp.nmb, nfull = sp.nfull, ngrp = sp.ngrp;
   hipStream_t s = (hipStream_t)stream;
@@ -984,6 +1015,73 @@ int cidnet_conv3x3_wgrad(const float* dY, long dy_bs, const float* X, long x_bs,
   hipLaunchKernelGGL(c3_reduce_kernel, dim3((unsigned)((ne + kC3RedElems - 1) / kC3RedElems)), dim3(256), 0, s, ws, B * chunks, ne, dW);
   CIDNET_LAUNCH_STATUS();
   return CIDNET_OK;
+}
+
+/* host only: what the launchers above (and conv3_thin / conv3x / conv3xw) will do for a problem; see cidnet_hip.h */
+int cidnet_conv3x3_tiling(int kind, int B, int M, int K, int H, int W, int levels, int* out, int n_out) {
+  static const int nfields[6] = {10, 10, 5, 4, 8, 5};
+  CIDNET_CHECK_ARG(out && kind >= 0 && kind <= 5 && n_out >= nfields[kind] && B > 0 && M > 0 && K > 0 && H > 0 && W > 0);
+  const bool thin = c3_thin_applies(M, K) && !(g_c3_dbg & 8);
+  int n = 0;
+  switch (kind) {
+    case 0: {   // cidnet_conv3x3 / cidnet_conv3x3_add
+      const WgSplit sp = wg_split(M, K);
+      const C3Tile t = c3_pick_tile(B, sp.nmb, K, H, W);
+      const C3Grid g = c3_grid(t.logx, t.tpb, H, W);
+      const int f[10] = {thin, sp.MT, sp.LEFT, sp.nmb, t.logx, t.tpb, t.narrow, g.ntiles, g.xt, g.gy};
+      for (; n < 10; ++n) out[n] = f[n];
+      return CIDNET_OK;
+    }
+    case 1: {   // cidnet_conv3x3_wgrad: dY has M planes, X has K
+      const WgSplit sp = wg_split(M, K);
+      int rr = 0, last = 0, chunks = 0, nitems = 0;
+      if (thin) {
+        chunks = c3_thin_wgrad_chunks(H, W);
+      } else {
+        rr = wg_rows(B, M, K, H, W);
+        chunks = wg_chunks(H, W, rr, &nitems);
+        last = H - ((H + rr - 1) / rr - 1) * rr;
+      }
+      const int f[10] = {thin ? 2 : (W < 8 ? 1 : 0), sp.MT, sp.LEFT, sp.nmb, sp.nfull, sp.ngrp, rr, last, chunks, nitems};
+      for (; n < 10; ++n) out[n] = f[n];
+      return CIDNET_OK;
+    }
+    case 2: {   // the streaming forward kernels
+      if (!thin) return CIDNET_ERR_SHAPE;
+      const C3ThinPlan p = c3_thin_plan(M, K, H, W);
+      const int f[5] = {p.kside, p.rows, p.nstrips, H - (p.nstrips - 1) * p.rows, (int)p.lds_bytes};
+      for (; n < 5; ++n) out[n] = f[n];
+      return CIDNET_OK;
+    }
+    case 3: {   // the streaming weight-gradient kernels
+      if (!thin) return CIDNET_ERR_SHAPE;
+      int rows, nstrips;
+      c3_thin_wgrad_strips(H, W, &rows, &nstrips);
+      const int f[4] = {c3_thin_wgrad_chunks(H, W), rows, nstrips, H - (nstrips - 1) * rows};
+      for (; n < 4; ++n) out[n] = f[n];
+      return CIDNET_OK;
+    }
+    case 4: {   // cidnet_conv3x3_bf16x3_pre_lv with `levels` activation levels
+      CIDNET_CHECK_ARG(levels == 1 || levels == 3);
+      if (!cidnet_conv3x3_bf16x3_supported(M, K)) return CIDNET_ERR_SHAPE;
+      const C3xPlan p = c3x_plan(B, M, K, H, W, levels);
+      if (p.nwork > 0x7fffffffL) return CIDNET_ERR_SHAPE;
+      // the kernel deals work ids XCD-wise when its grid is a multiple of 8; a block takes ids first, first + grid, ...
+      const int f[8] = {p.tiles_x, p.tiles_y, p.mchunks, p.kchunks, (int)p.nwork, (int)p.nblk, p.nblk % 8 == 0,
+                        (int)((p.nwork + p.nblk - 1) / p.nblk)};
+      for (; n < 8; ++n) out[n] = f[n];
+      return CIDNET_OK;
+    }
+    default: {  // cidnet_conv3x3_wgrad_bf16x3_lv: block x of a chunk pair takes tiles x, x + nblk, ...
+      CIDNET_CHECK_ARG(levels == 1 || levels == 3);
+      if (!cidnet_conv3x3_wgrad_bf16x3_supported(M, K, H, W)) return CIDNET_ERR_SHAPE;
+      const C3xwPlan p = c3xw_plan(B, M, K, H, W);
+      if (p.ntiles > 0x7fffffffL) return CIDNET_ERR_SHAPE;
+      const int f[5] = {p.pairs, p.nblk, (int)p.ntiles, (int)(p.ntiles / p.nblk), (int)((p.ntiles + p.nblk - 1) / p.nblk)};
+      for (; n < 5; ++n) out[n] = f[n];
+      return CIDNET_OK;
+    }
+  }
 }
 
 int cidnet_conv3x3_replicate_dgrad_fix(const float* gY, const float* Wt, float* gX, int B, int Co, int Ci, int H, int W,

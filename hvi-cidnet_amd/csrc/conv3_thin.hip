@@ -9,6 +9,7 @@
 #include "common.h"
 #include "stencil.h"
 #include "conv3_thin.h"
+#include "conv3_tiling.h"
 
 namespace cidnet {
 namespace {
@@ -302,6 +303,11 @@ __global__ __launch_bounds__(kThreads) void c3_thin_wgrad_m_kernel(ThinWgArgs a)
 }
 
 constexpr int kWgRows = 16;
+constexpr int kThinKRows = 8;                                  // strip height of the K-side kernel
+constexpr int thin_m_rows(int M) { return M == 1 ? 8 : 4; }    // strip height R of the M-side kernel
+// dynamic LDS: the weight panel [k][m][12] and the exchange buffer [3][R*M*4][64] (M side); the panel [m][k][12] (K side)
+inline size_t thin_m_lds(int M, int R, int K) { return ((size_t)K * M * 12 + (size_t)3 * R * M * 4 * 64) * sizeof(float); }
+inline size_t thin_k_lds(int M, int K) { return (size_t)M * K * 12 * sizeof(float); }
 
 }  // namespace
 
@@ -312,7 +318,7 @@ int launch_thin_m(ThinArgs a, int replicate, hipStream_t s) {
   a.st = make_strip(a.H, a.W, R);
   const long items = (long)a.B * a.st.nstrips * a.st.nx4;
   const dim3 grid((unsigned)((items + 63) / 64));
-  const size_t lds = ((size_t)a.K * M * 12 + (size_t)3 * R * M * 4 * 64) * sizeof(float);
+  const size_t lds = thin_m_lds(M, R, a.K);
   if (a.W < 8) {
     if (replicate) hipLaunchKernelGGL((c3_thin_m_kernel<M, R, true, true>), grid, dim3(kThreads), lds, s, a);
     else hipLaunchKernelGGL((c3_thin_m_kernel<M, R, false, true>), grid, dim3(kThreads), lds, s, a);
@@ -326,10 +332,10 @@ int launch_thin_m(ThinArgs a, int replicate, hipStream_t s) {
 
 template <int K>
 int launch_thin_k(ThinArgs a, int replicate, hipStream_t s) {
-  a.st = make_strip(a.H, a.W, 8);
+  a.st = make_strip(a.H, a.W, kThinKRows);
   const long items = (long)a.B * a.st.nstrips * a.st.nx4;
   const dim3 grid((unsigned)((items + kThreads - 1) / kThreads));
-  const size_t lds = (size_t)a.M * K * 12 * sizeof(float);
+  const size_t lds = thin_k_lds(a.M, K);
   if (a.W < 8) {
     if (replicate) hipLaunchKernelGGL((c3_thin_k_kernel<K, true, true>), grid, dim3(kThreads), lds, s, a);
     else hipLaunchKernelGGL((c3_thin_k_kernel<K, false, true>), grid, dim3(kThreads), lds, s, a);
@@ -346,10 +352,10 @@ int c3_thin_conv(const float* X, long x_bs, const float* Wt, long w_ms, long w_k
   const ThinArgs a{X, x_bs, Wt, w_ms, w_ks, Y, y_bs, B, M, K, H, W, flip, Strip{}};
   if (M <= 4) {
     switch (M) {
-      case 1: return launch_thin_m<1, 8>(a, replicate, s);
-      case 2: return launch_thin_m<2, 4>(a, replicate, s);
-      case 3: return launch_thin_m<3, 4>(a, replicate, s);
-      default: return launch_thin_m<4, 4>(a, replicate, s);
+      case 1: return launch_thin_m<1, thin_m_rows(1)>(a, replicate, s);
+      case 2: return launch_thin_m<2, thin_m_rows(2)>(a, replicate, s);
+      case 3: return launch_thin_m<3, thin_m_rows(3)>(a, replicate, s);
+      default: return launch_thin_m<4, thin_m_rows(4)>(a, replicate, s);
     }
   }
   switch (K) {
@@ -358,6 +364,21 @@ int c3_thin_conv(const float* X, long x_bs, const float* Wt, long w_ms, long w_k
     case 3: return launch_thin_k<3>(a, replicate, s);
     default: return launch_thin_k<4>(a, replicate, s);
   }
+}
+
+C3ThinPlan c3_thin_plan(int M, int K, int H, int W) {
+  C3ThinPlan p;
+  p.kside = M <= 4 ? 0 : 1;                                    // c3_thin_conv's dispatch
+  p.rows = p.kside ? kThinKRows : thin_m_rows(M);
+  const Strip st = make_strip(H, W, p.rows);
+  p.nx4 = st.nx4; p.nstrips = st.nstrips;
+  p.lds_bytes = (long)(p.kside ? thin_k_lds(M, K) : thin_m_lds(M, p.rows, K));
+  return p;
+}
+
+void c3_thin_wgrad_strips(int H, int W, int* rows, int* nstrips) {
+  const Strip st = make_strip(H, W, kWgRows);
+  *rows = st.rows; *nstrips = st.nstrips;
 }
 
 int c3_thin_wgrad_chunks(int H, int W) {

@@ -38,6 +38,7 @@
 // No packed-fp32 / SDWA instructions: built with -fno-slp-vectorize -mllvm -amdgpu-sdwa-peephole=0.
 #include "common.h"
 #include "cidnet_hip.h"
+#include "conv3_tiling.h"
 
 namespace cidnet {
 namespace {
@@ -49,6 +50,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int kXThreads = 256;
 constexpr int kXTH = 8, kXTW = 32, kXPH = kXTH + 2, kXPW = kXTW + 2;
 constexpr int kXMC = 48;                                    // output channels per block chunk (three 16-row tiles)
+constexpr int kXKCH = 36;                                   // input channels per chunk of the instantiated kernels
 
 constexpr int x3_row_pitch(int kch) {
   int rp = kXPW * kch + (8 * ((3 * kch + 7) / 8) - 3 * kch);  // pixels + the overrun of the last pixel's dy-run
@@ -410,6 +412,23 @@ __global__ __launch_bounds__(kXThreads, x3_blocks_per_cu(XL)) void conv3x_kernel
   }
 }
 
+}  // namespace
+
+// the launch plan: output tiles of 8 x 32 pixels x 48-channel chunks are the work items of a persistent grid
+C3xPlan c3x_plan(int B, int M, int K, int H, int W, int x_levels) {
+  C3xPlan p;
+  p.mchunks = (M + kXMC - 1) / kXMC;
+  p.kchunks = K / kXKCH;
+  p.tiles_x = (W + kXTW - 1) / kXTW;
+  p.tiles_y = (H + kXTH - 1) / kXTH;
+  p.nwork = (long)B * p.tiles_x * p.tiles_y * p.mchunks;
+  p.nblk = 256 * x3_blocks_per_cu(x_levels);                  // persistent: every resident slot of the 256 CUs
+  if (p.nblk > p.nwork) p.nblk = p.nwork;
+  return p;
+}
+
+namespace {
+
 template <int KCH>
 int launch_conv3x_prep(const float* Wt, long w_ms, long w_ks, int flip, int M, int K, float* ws, long ws_floats, hipStream_t s) {
   const int total = conv3x_prep_total<KCH>(M, K);
@@ -421,17 +440,17 @@ int launch_conv3x_prep(const float* Wt, long w_ms, long w_ks, int flip, int M, i
 template <int KCH, int WL, int XL>
 int launch_conv3x(X3Args a, const float* wprep, hipStream_t s) {
   using T = X3<KCH>;
-  a.mchunks = (a.M + kXMC - 1) / kXMC;
-  a.kchunks = a.K / KCH;
+  static_assert(KCH == kXKCH, "c3x_plan counts input chunks of kXKCH channels");
+  const C3xPlan pl = c3x_plan(a.B, a.M, a.K, a.H, a.W, XL);
+  a.mchunks = pl.mchunks;
+  a.kchunks = pl.kchunks;
   a.A = reinterpret_cast<const uint4*>(wprep);
-  a.tiles_x = (a.W + kXTW - 1) / kXTW;
-  a.tiles_y = (a.H + kXTH - 1) / kXTH;
+  a.tiles_x = pl.tiles_x;
+  a.tiles_y = pl.tiles_y;
   constexpr int lds_bytes = T::lds_bytes(XL);
   static LdsLimit lds;                                        // once per device: the kernel's dynamic-LDS limit
   if (const hipError_t e = lds.raise(reinterpret_cast<const void*>(&conv3x_kernel<KCH, WL, XL>), lds_bytes); e != hipSuccess) return (int)e;
-  const long nwork = (long)a.B * a.tiles_x * a.tiles_y * a.mchunks;
-  long nblk = 256 * x3_blocks_per_cu(XL);                     // persistent: every resident slot of the 256 CUs
-  if (nblk > nwork) nblk = nwork;
+  const long nblk = pl.nblk;
   a.stagger = 2;                                              // ~8k cycles: about the length of a staging phase
   hipLaunchKernelGGL((conv3x_kernel<KCH, WL, XL>), dim3((unsigned)nblk), dim3(kXThreads), lds_bytes, s, a);
   return CIDNET_OK;

@@ -31,6 +31,7 @@
 // No packed-fp32 / SDWA instructions (hvi-cidnet_amd/build.py).
 #include "common.h"
 #include "cidnet_hip.h"
+#include "conv3_tiling.h"
 
 namespace cidnet {
 namespace {
@@ -455,6 +456,17 @@ inline int w3_blocks_per_pair(int B, int M, int N, int H, int W) {
 }
 
 }  // namespace
+
+C3xwPlan c3xw_plan(int B, int M, int N, int H, int W) {
+  C3xwPlan p;
+  p.pairs = (M / kWC) * (N / kWC);
+  p.nblk = w3_blocks_per_pair(B, M, N, H, W);
+  p.tiles_x = (W + kWTW - 1) / kWTW;
+  p.tiles_y = (H + kWTH - 1) / kWTH;
+  p.ntiles = (long)B * p.tiles_x * p.tiles_y;
+  return p;
+}
+
 }  // namespace cidnet
 
 using namespace cidnet;
@@ -483,11 +495,12 @@ int cidnet_conv3x3_wgrad_bf16x3_lv(const float* dY, long dy_bs, const float* X, 
   CIDNET_CHECK_ARG(dY && X && dW && ws && B > 0 && M > 0 && N > 0 && H > 0 && W > 0 && (levels == 1 || levels == 3));
   if (!cidnet_conv3x3_wgrad_bf16x3_supported(M, N, H, W)) return CIDNET_ERR_SHAPE;
   if (ws_floats < cidnet_conv3x3_wgrad_bf16x3_ws_floats(B, M, N, H, W)) return CIDNET_ERR_WS;
-  W3Args a{dY, dy_bs, X, x_bs, ws, B, M, N, H, W, (W + kWTW - 1) / kWTW, (H + kWTH - 1) / kWTH, N / kWC};
+  const C3xwPlan pl = c3xw_plan(B, M, N, H, W);
+  W3Args a{dY, dy_bs, X, x_bs, ws, B, M, N, H, W, pl.tiles_x, pl.tiles_y, N / kWC};
 #ifdef CIDNET_DEBUG
   a.dbg = g_w3_dbg;
 #endif
-  const int nblk = w3_blocks_per_pair(B, M, N, H, W);
+  const int nblk = pl.nblk;
   static LdsLimit lds3, lds1;                                 // once per device: the kernels' dynamic-LDS limit
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)nblk, (unsigned)((M / kWC) * (N / kWC)));

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 12
+#define CIDNET_ABI_VERSION 13
 
 int cidnet_abi_version(void);
 
@@ -319,6 +319,24 @@ int cidnet_conv3x3_wgrad_bf16x3_lv(const float* dY, long dy_bs, const float* X, 
 void cidnet_debug_c3xw_flags(int flags);
 #endif
 /* Adds to gX (computed by the zero-pad data gradient) the taps that read replicated border pixels. */
+/* The tiling the 3x3 convolution launchers take for a problem; host only, launches nothing and touches no device.  Computed
+ * by the functions the launchers themselves call.  Writes the fields of `kind` to out[0..] (n_out >= 10 always suffices):
+ *  0  cidnet_conv3x3 / _add (M outputs, K inputs): thin (1: the streaming kernels of kind 2 run instead), MT, LEFT, nmb
+ *     (a block owns 16 MT + 4 LEFT output channels, nmb blocks cover M), LOGX (tile = 4 << LOGX pixels x 128 >> LOGX
+ *     rows), tpb (row tiles a block walks), narrow (W < 8), row tiles, tiles across, blocks down (grid = across x down x B nmb)
+ *  1  cidnet_conv3x3_wgrad (dY M planes, X K planes): path (0 MFMA, 1 narrow W < 8, 2 streaming kernels), MT, LEFT, nmb,
+ *     nfull (16-wide input tiles), ngrp (4-wide groups of the input remainder, their own launch), rr (rows per chunk),
+ *     rows of the last row chunk, chunks (workspace = B chunks M K 9 floats), work items (column tile x row chunk)
+ *  2  the streaming forward kernels (min(M, K) <= 4): kernel (0 M-side, 1 K-side), strip rows, strips, rows of the last
+ *     strip, dynamic LDS bytes
+ *  3  the streaming weight-gradient kernels: chunks (workspace = B chunks M K 9 floats), strip rows, strips, rows of the last
+ *  4  cidnet_conv3x3_bf16x3_pre_lv with `levels` activation levels (1 or 3): tiles_x, tiles_y, mchunks, kchunks, nwork (work
+ *     items), grid blocks, 1 if the kernel deals work ids XCD-wise (grid a multiple of 8), most work items of a block
+ *  5  cidnet_conv3x3_wgrad_bf16x3_lv (dY M planes, X K planes): chunk pairs, blocks per pair, tiles, fewest and most tiles
+ *     of a block (workspace = pairs x blocks per pair x 108 x 108 floats)
+ * `levels` is read by kinds 4 and 5 only.  CIDNET_ERR_SHAPE where the path does not take the shape (kinds 2, 3: not a thin
+ * layer; 4, 5: the *_supported predicates).  The tests assert through it that a case runs the tiling it is there for. */
+int cidnet_conv3x3_tiling(int kind, int B, int M, int K, int H, int W, int levels, int* out, int n_out);
 int cidnet_conv3x3_replicate_dgrad_fix(const float* gY, const float* Wt, float* gX, int B, int Co,
                                        int Ci, int H, int W, void* stream);
 

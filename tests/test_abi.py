@@ -67,6 +67,156 @@ def test_dw_tiling_query_contract():
         assert q(0, 4, 8, 8, *ptrs) == -1
 
 
+_C3_FIELDS = (("thin", "MT", "LEFT", "nmb", "LOGX", "tpb", "narrow", "ntiles", "xt", "gy"),
+              ("path", "MT", "LEFT", "nmb", "nfull", "ngrp", "rr", "last", "chunks", "nitems"),
+              ("kside", "rows", "nstrips", "last", "lds"), ("chunks", "rows", "nstrips", "last"),
+              ("tiles_x", "tiles_y", "mchunks", "kchunks", "nwork", "grid", "remap", "maxitems"),
+              ("pairs", "nblk", "ntiles", "nt_min", "nt_max"))
+
+
+def _c3_tiling(kind, B, M, K, H, W, levels=3):
+    """cidnet_conv3x3_tiling -> (status, {field: value}); the buffer is prefilled so that unwritten fields show"""
+    from hvi_cidnet_amd import _lib
+    out = (ctypes.c_int * 10)(*([-7] * 10))
+    rc = _lib.lib().raw("cidnet_conv3x3_tiling")(kind, B, M, K, H, W, levels, out, 10)
+    vals = list(out)
+    assert vals[len(_C3_FIELDS[kind]):] == [-7] * (10 - len(_C3_FIELDS[kind]))          # never past its own fields
+    if rc != 0:
+        assert vals == [-7] * 10                                                       # nothing written on an error
+    return rc, dict(zip(_C3_FIELDS[kind], vals))
+
+
+_C3_M = (1, 3, 4, 5, 12, 13, 17, 21, 24, 29, 32, 33, 36, 37, 48, 49, 50, 64, 65, 72, 97, 144, 145, 256, 257)
+_C3_PLANES = [(1, 1), (1, 9), (2, 7), (3, 8), (8, 16), (9, 16), (17, 16), (5, 13), (9, 63), (23, 65), (33, 40), (57, 70),
+              (100, 150), (273, 300), (417, 400)]
+
+
+def test_conv3x3_tiling_fp32_forward_contract():
+    """kind 0: the m-blocks cover M with MT + LEFT <= 3 accumulator sets, the tiles cover the plane exactly once, a block
+    walks tpb row tiles only while the weight panel stays resident (K <= 36), W < 8 is the NARROW instantiation"""
+    seen = set()
+    for M in _C3_M:
+        for K in (1, 4, 5, 12, 36, 37, 72):
+            for B in (1, 3):
+                for H, W in _C3_PLANES:
+                    rc, t = _c3_tiling(0, B, M, K, H, W)
+                    assert rc == 0
+                    what = (B, M, K, H, W, t)
+                    assert t["thin"] == int((M <= 4 and K <= 256) or (K <= 4 and M <= 256)), what
+                    mb = 16 * t["MT"] + 4 * t["LEFT"]
+                    assert t["MT"] >= 1 and 0 <= t["LEFT"] <= 2 and t["MT"] + t["LEFT"] <= 3, what
+                    assert t["nmb"] * mb >= M > (t["nmb"] - 1) * mb, what
+                    assert t["LOGX"] in (2, 3, 4) and t["narrow"] == int(W < 8) and (not t["narrow"] or t["LOGX"] == 2), what
+                    tw, th = 4 << t["LOGX"], 8 * (16 >> t["LOGX"])
+                    assert t["xt"] * tw >= W > (t["xt"] - 1) * tw and t["ntiles"] * th >= H > (t["ntiles"] - 1) * th, what
+                    assert 1 <= t["tpb"] <= (4 if K <= 36 else 1) and t["gy"] * t["tpb"] >= t["ntiles"] > (t["gy"] - 1) * t["tpb"], what
+                    seen.add((t["MT"], t["LEFT"]))
+                    seen.add(("tpb", t["tpb"]))
+    assert {(1, 0), (1, 1), (1, 2), (2, 0), (2, 1), (3, 0), ("tpb", 1), ("tpb", 2), ("tpb", 3)} <= seen
+
+
+def test_conv3x3_tiling_fp32_wgrad_contract():
+    """kinds 1 and 3: the row chunks cover H exactly once, the input tiles and groups cover N, and the workspace the fields
+    imply is cidnet_conv3x3_wgrad_ws_floats"""
+    from hvi_cidnet_amd import _lib
+    ws = _lib.lib().raw("cidnet_conv3x3_wgrad_ws_floats")
+    paths = set()
+    for M in _C3_M:
+        for N in (1, 4, 5, 8, 12, 16, 20, 24, 28, 36, 44, 72, 256):
+            for B in (1, 3):
+                for H, W in _C3_PLANES:
+                    rc, t = _c3_tiling(1, B, M, N, H, W)
+                    assert rc == 0
+                    what = (B, M, N, H, W, t)
+                    thin = (M <= 4 and N <= 256) or (N <= 4 and M <= 256)
+                    assert t["path"] == (2 if thin else 1 if W < 8 else 0), what
+                    paths.add(t["path"])
+                    assert ws(B, M, N, H, W) == B * t["chunks"] * M * N * 9, what
+                    rc3, t3 = _c3_tiling(3, B, M, N, H, W)
+                    assert rc3 == (0 if thin else -2), what
+                    if thin:
+                        nx4 = (W + 3) // 4
+                        assert t3["rows"] * t3["nstrips"] >= H > t3["rows"] * (t3["nstrips"] - 1), what
+                        assert t3["last"] == H - t3["rows"] * (t3["nstrips"] - 1), what
+                        assert t3["chunks"] == t["chunks"] == -(-t3["nstrips"] * nx4 // 256), what
+                        continue
+                    mb = 16 * t["MT"] + 4 * t["LEFT"]
+                    assert t["MT"] + t["LEFT"] <= 3 and t["nmb"] * mb >= M > (t["nmb"] - 1) * mb, what
+                    assert 0 <= t["ngrp"] <= 2 and 16 * t["nfull"] + 4 * t["ngrp"] >= N > 16 * (t["nfull"] - 1) + 4 * t["ngrp"], what
+                    nrc = -(-H // t["rr"])
+                    assert 1 <= t["last"] <= t["rr"] and (nrc - 1) * t["rr"] + t["last"] == H, what
+                    assert t["rr"] >= min(8, H), what
+                    assert t["nitems"] == -(-W // 32) * nrc and t["chunks"] == -(-t["nitems"] // 4), what
+    assert paths == {0, 1, 2}
+
+
+def test_conv3x3_tiling_thin_contract():
+    """kind 2: the strips cover H exactly once; the M side takes every layer with M <= 4; not a thin layer is the shape error"""
+    for M in _C3_M:
+        for K in (1, 2, 4, 5, 36, 85, 86, 200, 256, 257):
+            for H, W in _C3_PLANES:
+                rc, t = _c3_tiling(2, 2, M, K, H, W)
+                what = (M, K, H, W, t)
+                thin = (M <= 4 and K <= 256) or (K <= 4 and M <= 256)
+                assert rc == (0 if thin else -2), what
+                if not thin:
+                    continue
+                assert t["kside"] == int(M > 4), what
+                assert t["rows"] * t["nstrips"] >= H > t["rows"] * (t["nstrips"] - 1), what
+                assert t["last"] == H - t["rows"] * (t["nstrips"] - 1) and 1 <= t["last"] <= t["rows"], what
+                assert t["lds"] == (M * K * 48 if M > 4 else K * M * 48 + 3 * t["rows"] * M * 1024) <= 160 * 1024, what
+
+
+def test_conv3x3_tiling_bf16x3_contract():
+    """kinds 4 and 5: the tiles cover the plane exactly once, the persistent grids never exceed the work, every block's tile
+    count adds up to the tiles, the implied workspace is cidnet_conv3x3_wgrad_bf16x3_ws_floats, and the shape error agrees
+    with the *_supported predicates"""
+    from hvi_cidnet_amd import _lib
+    L = _lib.lib()
+    ws = L.raw("cidnet_conv3x3_wgrad_bf16x3_ws_floats")
+    planes = _C3_PLANES + [(1, 4), (12, 352), (36, 480), (50, 780), (9, 5473), (400, 600)]
+    many = set()
+    for M in (1, 35, 36, 47, 49, 72, 100, 144, 288):
+        for K in (12, 35, 36, 37, 72, 144):
+            for B in (1, 2, 8):
+                for H, W in planes:
+                    for lv in (1, 3):
+                        rc, t = _c3_tiling(4, B, M, K, H, W, lv)
+                        what = (B, M, K, H, W, lv, t)
+                        assert rc == (0 if L.raw("cidnet_conv3x3_bf16x3_supported")(M, K) else -2), what
+                        if rc == 0:
+                            assert t["tiles_x"] * 32 >= W > (t["tiles_x"] - 1) * 32 and t["tiles_y"] * 8 >= H > (t["tiles_y"] - 1) * 8, what
+                            assert t["mchunks"] * 48 >= M > (t["mchunks"] - 1) * 48 and t["kchunks"] * 36 == K, what
+                            assert t["nwork"] == B * t["tiles_x"] * t["tiles_y"] * t["mchunks"], what
+                            assert 1 <= t["grid"] == min(t["nwork"], 1024 if lv == 1 else 512), what
+                            assert t["remap"] == int(t["grid"] % 8 == 0) and t["maxitems"] == -(-t["nwork"] // t["grid"]), what
+                            many.add(t["maxitems"] > 1)
+                        rc, t = _c3_tiling(5, B, M, K, H, W, lv)
+                        what = (B, M, K, H, W, lv, t)
+                        assert rc == (0 if L.raw("cidnet_conv3x3_wgrad_bf16x3_supported")(M, K, H, W) else -2), what
+                        if rc == 0:
+                            assert t["pairs"] == (M // 36) * (K // 36) and 1 <= t["nblk"] <= t["ntiles"], what
+                            assert t["ntiles"] == B * -(-W // 32) * -(-H // 4), what
+                            nts = [(t["ntiles"] - x + t["nblk"] - 1) // t["nblk"] for x in range(t["nblk"])]      # the kernel's split
+                            assert sum(nts) == t["ntiles"] and min(nts) == t["nt_min"] >= 1 and max(nts) == t["nt_max"], what
+                            assert ws(B, M, K, H, W) == t["pairs"] * t["nblk"] * 108 * 108, what
+    assert many == {False, True}
+
+
+def test_conv3x3_tiling_bad_arguments():
+    from hvi_cidnet_amd import _lib
+    q = _lib.lib().raw("cidnet_conv3x3_tiling")
+    out = (ctypes.c_int * 10)()
+    assert q(0, 1, 12, 12, 8, 8, 3, out, 10) == 0
+    for bad in ((-1, 1, 12, 12, 8, 8, 3), (6, 1, 12, 12, 8, 8, 3), (0, 0, 12, 12, 8, 8, 3), (0, 1, 0, 12, 8, 8, 3), (1, 1, 12, -1, 8, 8, 3),
+                (0, 1, 12, 12, 0, 8, 3), (0, 1, 12, 12, 8, 0, 3), (4, 1, 36, 36, 8, 8, 2), (5, 1, 36, 36, 8, 8, 0)):
+        assert q(*bad, out, 10) == -1, bad
+    assert q(0, 1, 12, 12, 8, 8, 3, None, 10) == -1
+    for kind, n in enumerate((10, 10, 5, 4, 8, 5)):
+        shape = (1, 3, 36, 8, 8) if kind in (2, 3) else (1, 36, 36, 8, 8)
+        assert q(kind, *shape, 3, out, n) == 0 and q(kind, *shape, 3, out, n - 1) == -1, kind
+
+
 def test_product_path_refuses_cpu_tensors():
     import torch
     from hvi_cidnet_amd.hvi_transform import RGB_HVI
