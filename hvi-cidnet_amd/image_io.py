@@ -9,7 +9,18 @@ between two launches of this package's own kernels.
     q = enhance_u8(model, img_u8, gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0)
     report = enhance_folder(model, in_dir, out_dir, batch_size=8, threads=16)
 
-The kernels are csrc/imageio.hip (C ABI: cidnet_image_ingest / cidnet_image_egress, semantics in include/cidnet_hip.h).
+Large images, opt-in (tile=None, the default everywhere, is the path above, untouched):
+    plan = tile_plan(h, w, tile=1024, overlap=32)  # pure host code: overlapping windows of one shape over the padded image
+    x = ingest_tiles(img_u8, plan, gamma=1.0)      # uint8 (h,w,3) on the device -> fp32 (n,3,th,tw), cut from the bytes
+    q = egress_tiles(y, plan)                      # fp32 (n,3,th,tw) -> uint8 (h,w,3): blended by the plan's weights
+    q = enhance_u8(model, img_u8, tile=1024, overlap=32, tile_batch=8)
+    report = enhance_folder(model, in_dir, out_dir, tile=1024)
+The contract of the tiled mode is "the model applied to each window, blended by the plan's weights".  CIDNet's channel attention
+is global (the gram matrix and the q / k norms run over all pixels of a sample), so a tiled result is NOT the whole-image
+result and nothing is claimed about their distance; the reference has no such mode.
+
+The kernels are csrc/imageio.hip (C ABI: cidnet_image_ingest / cidnet_image_egress and their _tiles forms, semantics in
+include/cidnet_hip.h).
 
 enhance_folder is a pipeline; who owns what, and when:
   * decode workers (min(threads, 16)) read one file each through PIL's .convert('RGB') and write its bytes into a pinned
@@ -27,11 +38,13 @@ from __future__ import annotations
 
 import collections
 import concurrent.futures as cf
+import functools
 import os
 import threading
 import time
 from dataclasses import dataclass, field
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -135,21 +148,214 @@ def _run(model, t, table):
     return egress(out, hw)
 
 
+# ---- tiles: the plan (pure host code), window ingest, blended egress ----------------------------------------------------------
+@dataclass(eq=False)
+class TilePlan:
+    """Overlapping windows of one shape over the reflect-padded image (tile_plan).  size (h, w); padded (Hp, Wp); tile (th, tw);
+    ys, xs: the window origins per axis, ascending; origins: (n, 2) int32 (y, x), row-major over ys x xs; wy (len(ys), th) and
+    wx (len(xs), tw): fp32 blending weights per axis, strictly positive -- tile (ky, kx) weighs its pixel (i, j) with
+    wy[ky, i] * wx[kx, j].  The arrays are read-only; the device copies are made once per device and kept with the plan."""
+    size: tuple
+    padded: tuple
+    tile: tuple
+    ys: tuple
+    xs: tuple
+    origins: np.ndarray
+    wy: np.ndarray
+    wx: np.ndarray
+    _on: dict = field(default_factory=dict, repr=False)          # device index -> (origins, ys, xs, wy, wx) on that device
+
+    def __len__(self):
+        return len(self.ys) * len(self.xs)
+
+
+def _axis_origins(P, t, overlap):
+    """0, S, 2S, ... (S = t - overlap) while a tile fits, then one tile flush with the edge unless it repeats the last"""
+    if t == P:
+        return (0,)
+    S = t - overlap
+    o = list(range(0, P - t + 1, S))
+    if o[-1] != P - t:
+        o.append(P - t)
+    return tuple(o)
+
+
+def _axis_weights(o, t):
+    """a_k(i) = min(1, (i + 1) / (l_k + 1), (t - i) / (r_k + 1)), l_k / r_k the overlap of tile k with tile k - 1 / k + 1 (0 at
+    the ends): fp64, rounded once to fp32"""
+    i = np.arange(t, dtype=np.float64)
+    rows = []
+    for k, y in enumerate(o):
+        l = max(0, o[k - 1] + t - y) if k > 0 else 0
+        r = max(0, y + t - o[k + 1]) if k + 1 < len(o) else 0
+        rows.append(np.minimum(1.0, np.minimum((i + 1) / (l + 1), (t - i) / (r + 1))))
+    a = np.stack(rows).astype(np.float32)
+    a.flags.writeable = False
+    return a
+
+
+@functools.lru_cache(maxsize=64)
+def _tile_plan(h, w, Th, Tw, overlap, multiple):
+    if h <= 0 or w <= 0:
+        raise ValueError(f"tile_plan: the image must be positive (got {(h, w)})")
+    Hp, Wp = padded_size(h, w, multiple)
+    _check_reflect(h, w, Hp, Wp)
+    th, tw = min(Th, Hp), min(Tw, Wp)
+    if (th < Hp or tw < Wp) and 2 * overlap > min(th, tw):
+        raise ValueError(f"tile_plan: overlap {overlap} is more than half of the {(th, tw)} tile")
+    ys, xs = _axis_origins(Hp, th, overlap), _axis_origins(Wp, tw, overlap)
+    origins = np.array([(y, x) for y in ys for x in xs], dtype=np.int32).reshape(-1, 2)
+    origins.flags.writeable = False
+    return TilePlan((h, w), (Hp, Wp), (th, tw), ys, xs, origins, _axis_weights(ys, th), _axis_weights(xs, tw))
+
+
+def _check_tile(tile, overlap, multiple=8):
+    """what can be said of tile / overlap / multiple without an image -> (Th, Tw, overlap, multiple) as ints, or ValueError"""
+    pair = tuple(tile) if isinstance(tile, (tuple, list)) else (tile, tile)
+    if len(pair) != 2:
+        raise ValueError(f"tile_plan: tile must be T or (Th, Tw) (got {tile!r})")
+    Th, Tw, overlap, multiple = (_whole(v) for v in (*pair, overlap, multiple))
+    if multiple <= 0:
+        raise ValueError(f"multiple must be positive (got {multiple})")
+    if Th <= 0 or Tw <= 0:
+        raise ValueError(f"tile_plan: the tile must be positive (got {(Th, Tw)})")
+    if Th % multiple or Tw % multiple:
+        raise ValueError(f"tile_plan: the tile {(Th, Tw)} must be a multiple of {multiple}")
+    if overlap < 0:
+        raise ValueError(f"tile_plan: overlap must not be negative (got {overlap})")
+    return Th, Tw, overlap, multiple
+
+
+def _whole(v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer)) or v != v or v in (float("inf"), float("-inf")) \
+            or int(v) != v:
+        raise ValueError(f"tile_plan: sizes must be integers (got {v!r})")
+    return int(v)
+
+
+def tile_plan(h, w, tile, overlap=32, multiple=8) -> TilePlan:
+    """The windows of a (h, w) image for the tiled mode.  (Hp, Wp) = padded_size(h, w, multiple); tile = T or (Th, Tw), multiples
+    of `multiple`; (th, tw) = (min(Th, Hp), min(Tw, Wp)), so an image no larger than the tile is ONE tile of the padded image's
+    own shape.  Per axis the origins are 0, S, 2S, ... with S = t - overlap while a tile fits, then one last tile flush with
+    the edge (dropped when it repeats the previous one): every window lies inside the padded image, every pixel is covered, by
+    at most three tiles per axis.  ValueError for a non-positive size, a tile that is no multiple, an image that cannot be
+    reflected (pad >= side), a negative overlap, and 2 * overlap > min(th, tw) when there is more than one tile.  Plans are
+    cached (the last 64), and with them their device copies: one buffer of 4 (2 n + ny + nx + ny th + nx tw) bytes each."""
+    Th, Tw, overlap, multiple = _check_tile(tile, overlap, multiple)
+    return _tile_plan(_whole(h), _whole(w), Th, Tw, overlap, multiple)
+
+
+def _plan_on(plan, device):
+    """the plan's origins (n,2), ys, xs (int32) and wy, wx (fp32) on the device.  Uploaded once per plan and device: one packed
+    pinned buffer, one non-blocking copy on the current stream (nothing waits for the work already queued there); a later
+    caller's stream waits for that copy's event."""
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if key not in plan._on:
+        parts = (plan.origins.reshape(-1), np.asarray(plan.ys, dtype=np.int32), np.asarray(plan.xs, dtype=np.int32),
+                 plan.wy.reshape(-1).view(np.int32), plan.wx.reshape(-1).view(np.int32))
+        host = torch.empty(sum(a.size for a in parts), dtype=torch.int32, pin_memory=True)
+        np.concatenate(parts, out=host.numpy())
+        with torch.cuda.device(key):
+            buf = host.to(torch.device("cuda", key), non_blocking=True)
+            copied = torch.cuda.Event()
+            copied.record()
+        o, ys, xs, wy, wx = torch.split(buf, [a.size for a in parts])
+        tensors = (o.view(-1, 2), ys, xs, wy.view(torch.float32).view(len(plan.ys), -1), wx.view(torch.float32).view(len(plan.xs), -1))
+        plan._on[key] = (tensors, copied, host)                  # host: alive until the copy has run
+    tensors, copied, _ = plan._on[key]
+    torch.cuda.current_stream(key).wait_event(copied)
+    return tensors
+
+
+def _ingest_tiles(img, table, plan, lo=0, hi=None):
+    """tiles [lo, hi) of a checked dense (h,w,3) image -> (hi - lo,3,th,tw)"""
+    hi = len(plan) if hi is None else hi
+    h, w = plan.size
+    th, tw = plan.tile
+    x = torch.empty((hi - lo, 3, th, tw), dtype=torch.float32, device=img.device)
+    origins = _plan_on(plan, img.device)[0][lo:hi]
+    with torch.cuda.device(img.device):
+        lib().call("cidnet_image_ingest_tiles", ops._p(img), h, w, ops._p(table), ops._p(origins), ops._p(x), hi - lo, th, tw,
+                   ops._stream())
+    return x
+
+
+def _one_image(image_u8, plan, what):
+    t = _images_u8(image_u8, what)
+    if t.shape[0] != 1 or tuple(t.shape[1:3]) != tuple(plan.size):
+        raise RuntimeError(f"{what}: the plan is for one {plan.size} image, got {tuple(image_u8.shape)}")
+    return t[0]
+
+
+def ingest_tiles(image_u8: torch.Tensor, plan: TilePlan, gamma: float = 1.0) -> torch.Tensor:
+    """uint8 (h,w,3) (or (1,h,w,3)) on the device -> fp32 (n,3,th,tw): window t is ingest(image)[..., y:y+th, x:x+tw] at the
+    plan's origin t, cut straight from the bytes in one launch (the padded fp32 image never exists)."""
+    if isinstance(image_u8, torch.Tensor) and not image_u8.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    img = _one_image(image_u8, plan, "ingest_tiles")
+    return _ingest_tiles(img, _table_on(img.device, gamma), plan)
+
+
+def egress_tiles(tiles: torch.Tensor, plan: TilePlan) -> torch.Tensor:
+    """fp32 (n,3,th,tw) on the device, tile t at the plan's origin t -> uint8 (h,w,3) on the device: per pixel the weighted
+    mean, by the plan's wy * wx, of clamp(v, 0, 1) over the tiles that cover it (fp32, ascending tile order), the clamped value
+    itself where one tile covers it, then trunc(* 255.0f), interleaved.  NaN becomes 0.  A plan of one tile gives
+    egress(tiles[0], (h, w))."""
+    if not isinstance(tiles, torch.Tensor) or tiles.dtype != torch.float32:
+        raise RuntimeError(f"egress_tiles: expected an fp32 tensor (got {getattr(tiles, 'dtype', type(tiles).__name__)})")
+    if not tiles.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    if tuple(tiles.shape) != (len(plan), 3, *plan.tile):
+        raise RuntimeError(f"egress_tiles: expected {(len(plan), 3, *plan.tile)} for this plan, got {tuple(tiles.shape)}")
+    tiles = tiles.contiguous()
+    h, w = plan.size
+    _, ys, xs, wy, wx = _plan_on(plan, tiles.device)
+    q = torch.empty((h, w, 3), dtype=torch.uint8, device=tiles.device)
+    with torch.cuda.device(tiles.device):
+        lib().call("cidnet_image_egress_tiles", ops._p(tiles), ops._p(ys), len(plan.ys), ops._p(xs), len(plan.xs), ops._p(wy),
+                   ops._p(wx), ops._p(q), h, w, *plan.tile, ops._stream())
+    return q
+
+
+def _run_tiled(model, img, table, plan, tile_batch):
+    """window ingest -> the model over the tiles in chunks of tile_batch -> blended egress of a checked (h,w,3) image; the
+    caller holds the model's state.  Every chunk has the same shape, except possibly the last."""
+    n = len(plan)
+    out = torch.empty((n, 3, *plan.tile), dtype=torch.float32, device=img.device)
+    for lo in range(0, n, tile_batch):
+        hi = min(n, lo + tile_batch)
+        y = model(_ingest_tiles(img, table, plan, lo, hi))
+        out[lo:hi] = y[0] if isinstance(y, tuple) else y
+    return egress_tiles(out, plan)
+
+
+def _tile_batch(tile_batch):
+    if int(tile_batch) <= 0:
+        raise ValueError(f"tile_batch must be positive (got {tile_batch})")
+    return int(tile_batch)
+
+
 def _trans_attrs(gated, alpha_s, gated2, alpha):
     return dict(gated=bool(gated), alpha_s=float(alpha_s), gated2=bool(gated2), alpha=float(alpha))
 
 
 @torch.no_grad()
 def enhance_u8(model, images_u8: torch.Tensor, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3,
-               gated2: bool = False, alpha: float = 1.0) -> torch.Tensor:
+               gated2: bool = False, alpha: float = 1.0, tile=None, overlap: int = 32, tile_batch: int = 8) -> torch.Tensor:
     """uint8 (B,h,w,3) (or (h,w,3)) on the device -> the enhanced images, uint8 (B,h,w,3) on the device: ingest, the model in
     eval mode under no_grad with trans.gated / alpha_s / gated2 / alpha set (a tuple result -- CIDNet_TNSM -- gives its [0]),
-    egress.  The model's attributes and the train / eval mode of every submodule are restored afterwards."""
+    egress.  The model's attributes and the train / eval mode of every submodule are restored afterwards.
+    tile = T or (Th, Tw): each image runs as tile_plan(h, w, tile, overlap) -> window ingest -> the model over the tiles in
+    chunks of tile_batch -> blended egress; NOT the whole-image result (module docstring).  tile=None: the whole image."""
     if isinstance(images_u8, torch.Tensor) and not images_u8.is_cuda:
         raise RuntimeError(_NO_CPU)
     t = _images_u8(images_u8, "enhance_u8")
     _check_reflect(t.shape[1], t.shape[2], *padded_size(t.shape[1], t.shape[2]))
     table = _table_on(t.device, gamma)
+    if tile is not None:
+        plan, tile_batch = tile_plan(t.shape[1], t.shape[2], tile, overlap), _tile_batch(tile_batch)
+        with metrics._eval_state(model, _trans_attrs(gated, alpha_s, gated2, alpha)), torch.cuda.device(t.device):
+            return torch.stack([_run_tiled(model, img, table, plan, tile_batch) for img in t])
     with metrics._eval_state(model, _trans_attrs(gated, alpha_s, gated2, alpha)), torch.cuda.device(t.device):
         return _run(model, t, table)
 
@@ -255,11 +461,12 @@ class _Writer:
 class EnhanceReport:
     """What one rank's enhance_folder did: names / sizes (h, w) of its images in input order, batches (the input positions of
     each launch), seconds: {"wall": the call, "wait_for_slot": of it, the main thread waiting for a batch in flight to
-    finish so that its buffers come free}"""
+    finish so that its buffers come free}, tiles: with tile=, the number of tiles of each image (empty otherwise)"""
     names: list = field(default_factory=list)
     sizes: list = field(default_factory=list)
     batches: list = field(default_factory=list)
     seconds: dict = field(default_factory=dict)
+    tiles: list = field(default_factory=list)
 
 
 class _Stage:
@@ -287,7 +494,8 @@ def _decode(stop, path, name, stage):
 
 @torch.no_grad()
 def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
-                   alpha: float = 1.0, batch_size: int = 1, threads: int = 8, depth: int = 2, process_group=None) -> EnhanceReport:
+                   alpha: float = 1.0, batch_size: int = 1, threads: int = 8, depth: int = 2, process_group=None, tile=None,
+                   overlap: int = 32, tile_batch: int = 8) -> EnhanceReport:
     """eval.py / demo.py for a folder: every image file of in_dir (metrics.folder_images: its files and order) is enhanced as
     enhance_u8 does and saved to out_dir/<same file name> by PIL in the format its extension names (the reference's
     output_img.save(output_folder + name[0])); out_dir is created.  Decoding, the device and encoding overlap (module
@@ -295,7 +503,9 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
     equal size sharing a batch of up to batch_size.  depth=1, threads=1 is the serial order; the files do not depend on any of
     the three.  With a process group (or an initialised default group) rank r takes images i % world == r; no collective runs
     and each rank reports its own images.  The first error of a worker stops the pipeline and is raised naming the file.
-    The model's attributes and modes are restored afterwards."""
+    The model's attributes and modes are restored afterwards.
+    tile = T or (Th, Tw): every image is tiled on its own as enhance_u8(tile=, overlap=, tile_batch=) does, one image per
+    launch group (batch_size is ignored); the pipeline around it is the same.  report.tiles holds each image's tile count."""
     t_start = time.perf_counter()
     device = metrics._model_device(model)
     if device.type != "cuda":
@@ -307,6 +517,9 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
     if process_group is not None or (dist.is_available() and dist.is_initialized()):
         world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
     batch_size, depth = max(1, int(batch_size)), max(1, int(depth))
+    if tile is not None:                                         # a bad tile / overlap / tile_batch raises before a worker starts
+        _check_tile(tile, overlap)
+        batch_size, tile_batch = 1, _tile_batch(tile_batch)
     workers = max(1, min(int(threads), 16))
     mine = list(shard(len(files), rank, world))
     report = EnhanceReport(names=[files.names[i] for i in mine])
@@ -359,6 +572,7 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
                 _, h, w = batch[0]
                 try:
                     _check_reflect(h, w, *padded_size(h, w))
+                    plan = tile_plan(h, w, tile, overlap) if tile is not None else None
                 except ValueError as e:
                     raise ValueError(f"enhance_folder: {files.names[positions[0]]}: {e}") from None
                 while len(writer.inflight) >= depth:             # the device input of this slot belongs to a batch in flight
@@ -374,7 +588,11 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
                 uploaded = torch.cuda.Event()
                 uploaded.record(up)
                 torch.cuda.current_stream().wait_event(uploaded)
-                q = _run(model, t, table)
+                if plan is None:
+                    q = _run(model, t, table)
+                else:
+                    q = _run_tiled(model, t[0], table, plan, tile_batch).unsqueeze(0)
+                    report.tiles.append(len(plan))
                 stages = [b[0] for b in batch]
                 writer.put(q, [os.path.join(out_dir, files.names[i]) for i in positions], on_done=lambda s=stages: free.extend(s))
                 report.batches.append(positions)

@@ -12,7 +12,8 @@
  *     "HW" planes are H*W floats; pointers are plain device pointers owned by the caller;  the one
  *     exception are the evaluation metrics (cidnet_metric_*), whose images are uint8 (B,3,h,w) and
  *     whose results are fp64 device buffers, the training-batch kernel (cidnet_augment_*), which reads a uint8 arena, and
- *     the image ingest / egress kernels (cidnet_image_*), whose byte side is interleaved (h,w,3) uint8;
+ *     the image ingest / egress kernels (cidnet_image_*), whose byte side is interleaved (h,w,3) uint8 and whose
+ *     tiled forms take int32 origin lists;
  *   - `stream` is a hipStream_t passed as void* (the caller's current stream; NULL = default);
  *   - functions are stateless and re-entrant, never allocate, never synchronise and never copy to
  *     the host, so a caller may capture them into a hipGraph;  scratch memory comes in through
@@ -29,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 13
+#define CIDNET_ABI_VERSION 14
 
 int cidnet_abi_version(void);
 
@@ -607,6 +608,32 @@ int cidnet_augment_crop_flip(const uint8_t* arena, const long* plan, const float
 int cidnet_image_ingest(const uint8_t* src, long src_bs, const float* table, float* x, int B, int h, int w, int Hp, int Wp,
                         void* stream);
 int cidnet_image_egress(const float* x, uint8_t* dst, long dst_bs, int B, int Hp, int Wp, int h, int w, void* stream);
+
+/* ---- Tiled enhancement of one large image (hvi-cidnet_amd/image_io.py: tile_plan): the same two conversions seen through
+ * overlapping windows of one fixed shape (th, tw), both multiples of 4.  The reference has no such mode; the contract is "the
+ * model applied to each window of the reflect-padded image, blended by the plan's weights".
+ * ingest_tiles: one (h,w,3) uint8 image (any byte alignment) -> x (n,3,th,tw) fp32.  origins: n rows of 2 int32 on the device,
+ *   (y_t, x_t), the window's top-left corner in the padded image.  x[t,c,i,j] = T[src[ry,rx,c]] with ry = y_t + i, reflected
+ *   as 2(h-1) - ry when ry >= h, and likewise rx = x_t + j against w: cidnet_image_ingest's arithmetic and table (NULL: fp32(q)
+ *   / 255.0f) through a window.  The origins live on the device and cannot be checked here without a copy: EVERY WINDOW MUST
+ *   LIE INSIDE THE PADDED IMAGE OF A PAD SMALLER THAN THE SIDE, CHECKED ON THE HOST WHERE THE PLAN WAS MADE (tile_plan does).
+ *   The kernel clamps a coordinate that a broken plan would put outside the image, so that even then only the 3 h w bytes of
+ *   the image are read.  n > 65535 or more than 2^30 groups of four pixels per tile is CIDNET_ERR_SHAPE.
+ * egress_tiles: tiles (ny * nx,3,th,tw) fp32, tile (ky, kx) at index ky * nx + kx with its corner at (origins_y[ky],
+ *   origins_x[kx]) (int32 on the device, ascending), and the weight tables wy (ny,th), wx (nx,tw) fp32 on the device ->
+ *   dst (h,w,3) uint8.  A gather over the output pixels (y, x), y < h, x < w: for every tile that covers the pixel, ky
+ *   ascending and kx ascending within it, with a = wy[ky, y - origins_y[ky]] * wx[kx, x - origins_x[kx]] (one fp32 product) and
+ *   v = clamp(tile value, 0, 1), NaN -> 0:  acc += a * v, den += a, in fp32.  The value is acc / den (a correctly rounded
+ *   fp32 division); A PIXEL COVERED BY EXACTLY ONE TILE TAKES v ITSELF, with no product and no division, so a plan of one tile
+ *   writes what cidnet_image_egress writes; a pixel no tile covers is written as 0.  dst[y,x,c] = (uint8) trunc(value *
+ *   255.0f).  Exactly the 3 h w bytes of dst are written, and only values inside the tiles and the tables are read, whatever
+ *   the origin lists hold.  ny or nx > 1024, or more than 2^30 groups of four pixels, is CIDNET_ERR_SHAPE.
+ * Both: th or tw not a multiple of 4 is CIDNET_ERR_SHAPE.  No atomics: a value depends on its own pixel's tiles alone, bit-
+ * identical from call to call. */
+int cidnet_image_ingest_tiles(const uint8_t* src, int h, int w, const float* table, const int* origins, float* x, int n, int th,
+                              int tw, void* stream);
+int cidnet_image_egress_tiles(const float* tiles, const int* origins_y, int ny, const int* origins_x, int nx, const float* wy,
+                              const float* wx, uint8_t* dst, int h, int w, int th, int tw, void* stream);
 
 #ifdef __cplusplus
 }

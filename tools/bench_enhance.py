@@ -12,7 +12,15 @@
                     to_uint8 -> .cpu() -> save, one thread), alternated, three times each: images per second, their ratio, and
                     the share of the pipelined run that the main thread spent waiting for a batch in flight
 
+  large             (--images mixed | big, optionally --tile N) a folder written by this tool -- mixed: eight images of eight
+                    sizes between 2.2 and 3.1 megapixels; big: one 4096 x 6144 image -- through enhance_folder(tile=N) (N absent:
+                    the whole image per launch), once to warm up and three times timed: wall seconds and megapixels per second.
+                    With --tile also the two tile kernels alone on the largest image's plan: time per launch, bytes from shapes
+                    -- 15 per tile pixel in, 12 per tile pixel + 3 per image pixel out -- and achieved bytes per second.
+                    --tile alone implies --images mixed.  Nothing else runs in this mode.
+
     python tools/bench_enhance.py [--launches 200] [--files 64] [--dir DIR] [--skip-pipeline]
+    python tools/bench_enhance.py --images mixed [--tile 1024] [--tile_overlap 32] [--tile_batch 8]
 """
 import argparse
 import json
@@ -154,8 +162,70 @@ def pipeline(folder, files):
                       "all_ratios_same_rep": [p / s for p, s in zip(rates["pipelined"], rates["serial"])]}), flush=True)
 
 
+MIXED = [(1200, 1800), (1808, 1208), (1400, 2100), (1365, 2048), (1536, 2048), (2048, 1536), (1250, 1875), (1333, 2000)]
+BIG = [(4096, 6144)]
+
+
+def _write_sizes(folder, sizes):
+    import numpy as np
+    from PIL import Image
+    os.makedirs(folder, exist_ok=True)
+    rng = np.random.default_rng(0)
+    for i, (h, w) in enumerate(sizes):
+        base = rng.integers(0, 96, size=(h // 16, w // 16, 3), dtype=np.uint8)           # smooth dark content, as _write_folder
+        Image.fromarray(base).resize((w, h), Image.BICUBIC).save(os.path.join(folder, f"{i:04d}.bmp"))   # .bmp: no codec time
+
+
+def large(folder, which, tile, overlap, tile_batch, launches):
+    import torch
+    import hvi_cidnet_amd as P
+    from hvi_cidnet_amd import metrics as M
+    dev = torch.device("cuda:0")
+    sizes = MIXED if which == "mixed" else BIG
+    src = os.path.join(folder, "in")
+    _write_sizes(src, sizes)
+    torch.manual_seed(0)
+    model = P.CIDNet().to(dev).eval()
+    listing = M.folder_images(src)
+    mp = sum(h * w for h, w in sizes) / 1e6
+    kw = dict(alpha_s=1.0, alpha=1.0, threads=16, depth=2, tile=tile, overlap=overlap, tile_batch=tile_batch)
+    for rep in range(-1, 3):                                     # -1: warm-up (code objects, allocator, every shape)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = P.enhance_folder(model, listing, os.path.join(folder, "out"), **kw)
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        print(json.dumps({"what": "large", "images": which, "tile": tile, "overlap": overlap if tile else None,
+                          "tile_batch": tile_batch if tile else None, "rep": rep, "files": len(sizes), "megapixels": mp, "s": t,
+                          "megapixels_per_s": mp / t, "tiles": r.tiles, "wait_for_slot_s": r.seconds["wait_for_slot"],
+                          "max_memory_allocated": torch.cuda.max_memory_allocated()}), flush=True)
+    if tile is None:
+        return
+    h, w = max(sizes, key=lambda s: s[0] * s[1])
+    plan = P.tile_plan(h, w, tile, overlap)
+    n, (th, tw) = len(plan), plan.tile
+    img = torch.randint(0, 256, (h, w, 3), dtype=torch.uint8, device=dev)
+    y = torch.rand((n, 3, th, tw), device=dev) * 1.2 - 0.1
+    for gamma in (1.0, 1.4):
+        P.ingest_tiles(img, plan, gamma=gamma)
+        _line("ingest_tiles", (h, w), launches, _events(lambda: P.ingest_tiles(img, plan, gamma=gamma), launches), 15 * n * th * tw,
+              gamma=gamma, tile=[th, tw], tiles=n)
+    P.egress_tiles(y, plan)
+    _line("egress_tiles", (h, w), launches, _events(lambda: P.egress_tiles(y, plan), launches), 12 * n * th * tw + 3 * h * w,
+          tile=[th, tw], tiles=n)
+    Hp, Wp = plan.padded
+    x = torch.rand((1, 3, Hp, Wp), device=dev)
+    P.ingest(img), P.egress(x, (h, w))                           # the untiled kernels on the same image, as yardsticks
+    _line("ingest", (1, h, w), launches, _events(lambda: P.ingest(img), launches), image_bytes(h, w, Hp, Wp), gamma=1.0)
+    _line("egress", (1, h, w), launches, _events(lambda: P.egress(x, (h, w)), launches), image_bytes(h, w, Hp, Wp))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--images", choices=("mixed", "big"), default=None, help="the large-image mode (module docstring)")
+    ap.add_argument("--tile", type=int, default=None)
+    ap.add_argument("--tile_overlap", type=int, default=32)
+    ap.add_argument("--tile_batch", type=int, default=8)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--files", type=int, default=64)
     ap.add_argument("--dir", default=None, help="where the synthetic folder and the outputs go (default: a temporary directory)")
@@ -165,6 +235,10 @@ def main():
     import torch
     if not torch.cuda.is_available():
         sys.exit("bench_enhance.py measures on a ROCm device; there is none")
+    if a.images or a.tile:
+        with tempfile.TemporaryDirectory(dir=a.dir) as d:
+            large(d, a.images or "mixed", a.tile, a.tile_overlap, a.tile_batch, max(50, a.launches))
+        return
     if not a.skip_kernels:
         kernels(max(200, a.launches))
     if not a.skip_pipeline:
