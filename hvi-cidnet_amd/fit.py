@@ -21,7 +21,9 @@ What differs from the reference's loop:
     (`start_epoch` > 0: weights only, fresh Adam, restarted warm-up, shortened cosine period) is kept as it is;
   * left out: the per-epoch training/test.png dump of the step's own output (the validation's enhanced images can be written:
     val_args=dict(save_dir=...), metrics.evaluate), the metrics .md table (on_epoch hands the numbers to the caller), the
-    option parser, the cyclic scheduler variant, LPIPS (metrics.py), the folder sampling of SICE / SID / LOL-blur.
+    option parser, the cyclic scheduler variant, LPIPS (metrics.py), the two-stage TRAINING folder sampling of SICE / SID /
+    LOL-blur (evaluating those sets is there: val_args=dict(resize=True) for labels of another size, and
+    metrics.nested_folder_pairs for the one-sub-folder-per-scene layout of SID / LOL-blur).
 """
 from __future__ import annotations
 

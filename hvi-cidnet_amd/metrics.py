@@ -4,10 +4,14 @@ also writes the files eval.py writes (image_io's egress kernel and writer), whic
 
     from hvi_cidnet_amd import metrics as M
     q = M.to_uint8(rgb, size=(h, w))        # fp32 (B,3,Hp,Wp) -> uint8 (B,3,h,w): clamp, x255, truncate, crop
+    r = M.resize_u8(q, (h2, w2))            # uint8 (B,3,h,w) -> uint8 (B,3,h2,w2): PIL's Image.resize, byte for byte
     p = M.psnr(q, gt_u8, gt_mean=False)     # (B,) float64 on the device, no host synchronisation
     s = M.ssim(q, gt_u8, gt_mean=False)     # (B,) float64 on the device
-    res = M.evaluate(model, pairs, gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0, batch_size=1, save_dir=None)
+    res = M.evaluate(model, pairs, gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0, batch_size=1, save_dir=None,
+                     resize=False)
     pairs = M.folder_pairs(low_dir, high_dir)
+    pairs = M.nested_folder_pairs(low_root, high_root, gt="name")      # LOL-Blur / SID: one sub-folder per scene
+    per_folder, overall = M.group_means(res, pairs)
 
 and, for the sets without ground truth (eval.py --unpaired + measure_niqe_bris.py), NIQE:
 
@@ -17,13 +21,14 @@ and, for the sets without ground truth (eval.py --unpaired + measure_niqe_bris.p
     res = M.evaluate_unpaired(model, images, prm, alpha=1.0, gamma=1.0, batch_size=1, save_dir=None)
     images = M.folder_images(dir)
 
-The kernels are csrc/metrics.hip and csrc/niqe.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
+The kernels are csrc/metrics.hip, csrc/resize.hip and csrc/niqe.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
 Differences from the reference scripts, none of which changes a per-image value:
   * measure.py counts a low image without a ground truth in the divisor of its averages (it skips the image after
     `n += 1`); here such an image is skipped and reported (FolderPairs.skipped, EvalResult.skipped) and not counted;
   * eval.py leaves `trans.alpha` (and with it the model's state) as the last run set it; evaluate() restores every
     attribute it touches and the train / eval mode of every submodule;
-  * a ground truth whose size differs from the output raises (measure.py:134 would bicubic-resize the output);
+  * a ground truth whose size differs from the output raises unless evaluate(resize=True) is asked for; then the quantized
+    output is resized as measure.py:133-134 resizes it (resize_u8: Pillow >= 7's default filter, byte for byte);
   * PSNR sums its squared errors exactly (fp64) where measure.py averages in fp32: < 1e-4 dB apart;
   * LPIPS is not computed (it needs AlexNet weights and the lpips package's heads);
   * NIQE: the half-size image sums its 8 taps in fp64 and rounds once per pass where the reference sums them in fp32 (two
@@ -86,6 +91,98 @@ def to_uint8(rgb: torch.Tensor, size=None) -> torch.Tensor:
     with torch.cuda.device(x.device):
         lib().call("cidnet_metric_to_uint8", ops._p(x), ops._p(q), B, Hp, Wp, h, w, ops._stream())
     return q[0] if squeeze else q
+
+
+# ---- PIL's 8-bit bicubic resize (measure.py:133-134) ----------------------------------------------------------------------
+_RESIZE_BITS = 22                                                  # Pillow's PRECISION_BITS for 8-bit images
+_resize_plans = {}                                                 # (n_in, n_out) -> (bounds, coeffs)
+_resize_plans_dev = {}                                             # (device index, n_in, n_out) -> (bounds, coeffs, ksize) there
+
+
+def _bicubic(x: float) -> float:
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def resize_plan(n_in: int, n_out: int):
+    """Pillow's coefficient tables for one axis of an 8-bit bicubic resize over the whole axis (Resample.c: precompute_coeffs
+    + normalize_coeffs_8bpc, restated; every operation in IEEE double, in Pillow's order) -> (bounds int32 (n_out, 2): first
+    tap, tap count; coeffs int32 (n_out, ksize): the normalised weights scaled by 2^22 and rounded half away from zero, rows
+    padded with zeros).  Cached per (n_in, n_out); the arrays are read-only."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"resize_plan: sizes must be positive (got {n_in} -> {n_out})")
+    key = (n_in, n_out)
+    if key in _resize_plans:
+        return _resize_plans[key]
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    bounds = np.zeros((n_out, 2), dtype=np.int32)
+    coeffs = np.zeros((n_out, ksize), dtype=np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)                 # int(): C's truncation
+        xmax = min(int(center + support + 0.5), n_in) - xmin
+        w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        bounds[xx] = (xmin, xmax)
+        for x, v in enumerate(w):
+            coeffs[xx, x] = int(v * (1 << _RESIZE_BITS) + (-0.5 if v < 0 else 0.5))
+    bounds.setflags(write=False)
+    coeffs.setflags(write=False)
+    _resize_plans[key] = (bounds, coeffs)
+    return bounds, coeffs
+
+
+def _resize_plan_on(device, n_in, n_out):
+    """uploaded once per process, device and (n_in, n_out)"""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), n_in, n_out)
+    if key not in _resize_plans_dev:
+        bounds, coeffs = resize_plan(n_in, n_out)
+        _resize_plans_dev[key] = (torch.from_numpy(bounds.copy()).to(device), torch.from_numpy(coeffs.copy()).to(device),
+                                  coeffs.shape[1])
+    return _resize_plans_dev[key]
+
+
+def resize_u8(q: torch.Tensor, size) -> torch.Tensor:
+    """uint8 (B,3,H,W) (or (3,H,W)) on the device -> uint8 (B,3,h,w), (h, w) = `size`: what PIL.Image.resize((w, h)) of
+    Pillow >= 7 returns for each 8-bit RGB image, byte for byte -- the default filter (antialiased bicubic, a = -0.5) over the
+    whole image with reducing_gap=None, in Pillow's fixed-point arithmetic: the horizontal pass first, rounded to uint8, then
+    the vertical one; an axis that keeps its size is not touched (measure.py:133-134).  `size` equal to the input's returns
+    the input itself.  (Pillow < 7 defaulted to nearest-neighbour: not reproduced, nor any other filter.)"""
+    _on_device(q)
+    if q.dtype != torch.uint8:
+        raise RuntimeError(f"resize_u8 takes uint8 images (got {q.dtype}); see to_uint8")
+    h, w = int(size[0]), int(size[1])
+    if h <= 0 or w <= 0:
+        raise ValueError(f"resize_u8: size {(h, w)} must be positive")
+    if q.dim() in (3, 4) and tuple(q.shape[-2:]) == (h, w) and q.shape[-3] == 3:
+        return q
+    squeeze = q.dim() == 3
+    x = _batched(q, "resize_u8")
+    B, _, H, W = x.shape
+    L = lib()
+    out = torch.empty((B, 3, h, w), dtype=torch.uint8, device=x.device)
+    n_tmp = L.raw("cidnet_metric_resize_ws_bytes")(B, H, W, h, w)
+    tmp = torch.empty(n_tmp, dtype=torch.uint8, device=x.device) if n_tmp else None
+    bx, cx, kx = _resize_plan_on(x.device, W, w) if W != w else (None, None, 0)
+    by, cy, ky = _resize_plan_on(x.device, H, h) if H != h else (None, None, 0)
+    with torch.cuda.device(x.device):
+        L.call("cidnet_metric_resize_u8", ops._p(x), ops._p(out), ops._p(tmp), ops._p(bx), ops._p(cx), kx, ops._p(by), ops._p(cy),
+               ky, B, H, W, h, w, ops._stream())
+    return out[0] if squeeze else out
 
 
 def psnr_ssim(restored: torch.Tensor, gt: torch.Tensor, gt_mean: bool = False, want_psnr: bool = True,
@@ -182,6 +279,7 @@ class EvalResult:
     per_image: dict = field(default_factory=dict)     # "psnr" / "ssim" / "psnr_gt_mean" / "ssim_gt_mean" -> list, input order
     names: list = field(default_factory=list)
     skipped: list = field(default_factory=list)       # low images without a ground truth (folder_pairs)
+    resized: list = field(default_factory=list)       # indices of the pairs whose output was resized to the ground truth's size
 
 
 _KEYS = ("psnr", "ssim", "psnr_gt_mean", "ssim_gt_mean")
@@ -246,12 +344,13 @@ def _plan(sizes, rank, world, batch_size):
 
 @torch.no_grad()
 def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, alpha, gamma, batch_size, process_group,
-              save_dir=None):
+              save_dir=None, run_key=None):
     """The evaluation loop of evaluate() and evaluate_unpaired(), `who` / `noun` naming them in errors.  load(i, item, device)
     -> (input fp32 (3,h,w), what score needs of the image); trans_attrs: the model.trans attributes set for the run; score(q
     uint8 (B,3,h,w), [load's second values]) -> one (B,) fp64 device tensor per key; result(alpha=, per_image=, names=,
     <key>=mean ...) builds the result for one alpha.  save_dir: every scored image is also written there (image_io's egress
-    kernel and writer), under items.names[i] or "<i as 5 digits>.png"."""
+    kernel and writer), under items.names[i] or "<i as 5 digits>.png" (a name may hold sub-folders: they are created).
+    run_key(load's second value): what, beside the crop size, the samples of one score() call must share."""
     device = _model_device(model)
     if not device.type == "cuda":
         raise RuntimeError(_NO_CPU)
@@ -284,7 +383,7 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
             x, aux = load(i, items[i], device)
             xp, hw = pad_to_multiple(x.unsqueeze(0), 8)
             loaded.append((xp, hw, aux))
-            yield xp.shape, hw
+            yield xp.shape, (hw if run_key is None else (hw, run_key(aux)))
     try:
         with _eval_state(model, trans_attrs) as trans, torch.cuda.device(device):
             for lo, hi, runs in _plan(sizes(), rank, world, max(1, int(batch_size))):
@@ -308,9 +407,11 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
                             into[:, col].copy_(v)
                         if writer is not None:
                             ids = range(rows.start, rows.stop, rows.step)
-                            writer.put(image_io.egress(out[j:k], batch[j][1]),
-                                       [os.path.join(save_dir, str(file_names[i]) if file_names is not None else f"{i:05d}.png")
-                                        for i in ids])
+                            paths = [os.path.join(save_dir, str(file_names[i]) if file_names is not None else f"{i:05d}.png")
+                                     for i in ids]
+                            for d in {os.path.dirname(p) for p in paths}:
+                                os.makedirs(d, exist_ok=True)
+                            writer.put(image_io.egress(out[j:k], batch[j][1]), paths)
             if writer is not None:
                 writer.close()
                 writer = None
@@ -335,7 +436,7 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
 
 
 def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
-             alpha=1.0, batch_size: int = 1, process_group=None, save_dir=None):
+             alpha=1.0, batch_size: int = 1, process_group=None, save_dir=None, resize: bool = False):
     """eval.py + measure.py on the device.  `pairs`: a sequence of (low, gt) -- low a (3,h,w) float image in [0, 1] (or a
     uint8 HWC image, converted as ToTensor() does), gt uint8 HWC / CHW or a float ToTensor() image of the same size
     (folder_pairs() yields these).  Each input is reflect-padded to a multiple of 8, run through model(pow(x, gamma)) in eval
@@ -351,21 +452,39 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     save_dir: each scored image is also written to save_dir/<name> (pairs.names[i] where the pairs have names, else
     "<i as 5 digits>.png") by PIL in the format the name's extension gives -- the files eval.py writes and measure.py reads;
     each rank writes its own images.  ValueError together with an alpha sweep.  None: nothing is written.
+    resize: False -- a ground truth whose size differs from its input's is a ValueError.  True -- such a pair is scored as
+    measure.py:133-134 scores it: the quantized output is resized to the ground truth's size (resize_u8: Pillow >= 7's default
+    bicubic, byte for byte; per alpha of a sweep) and GT mean, PSNR and SSIM are taken from the resized image; the pairs'
+    indices are reported in EvalResult.resized.  save_dir still receives the un-resized output, as eval.py writes it.  A
+    ground truth smaller than 11 x 11 raises as ssim() does.
     The model's attributes and the train / eval mode of every submodule are restored afterwards."""
     def load(i, pair, device):
         x, g = _image_f32(pair[0], device), _gt_u8(pair[1], device)
-        if tuple(g.shape) != tuple(x.shape):
+        if tuple(g.shape) != tuple(x.shape) and not resize:
             raise ValueError(f"evaluate: image {i}: ground truth {tuple(g.shape[1:])} and input {tuple(x.shape[1:])} "
-                             "differ in size (resizing the ground truth is not supported)")
+                             "differ in size (resize=True scores the output resized to the ground truth's size, as "
+                             "measure.py does)")
         return x, g
 
     def score(q, gts):
         g = torch.stack(gts) if len(gts) > 1 else gts[0].unsqueeze(0)
-        return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True))
+        if not resize:
+            return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True))
+        # the samples of a run share the ground truth's size (run_key); the flag column travels with the values, so that
+        # every rank of a sharded evaluation reports the same indices
+        flag = torch.full((q.shape[0],), float(q.shape[-2:] != g.shape[-2:]), dtype=torch.float64, device=q.device)
+        q = resize_u8(q, g.shape[-2:])
+        return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True), flag)
     skipped = list(getattr(pairs, "skipped", []))
+
+    def result(per_image, **kw):
+        flags = per_image.pop("resized", [])
+        kw.pop("resized", None)
+        return EvalResult(skipped=skipped, per_image=per_image, resized=[i for i, f in enumerate(flags) if f], **kw)
     return _evaluate("evaluate", "image pairs", model, pairs, load,
-                     dict(gated=bool(gated), alpha_s=float(alpha_s), gated2=bool(gated2)), score, _KEYS,
-                     lambda **kw: EvalResult(skipped=skipped, **kw), alpha, gamma, batch_size, process_group, save_dir)
+                     dict(gated=bool(gated), alpha_s=float(alpha_s), gated2=bool(gated2)), score,
+                     _KEYS + ("resized",) if resize else _KEYS, result, alpha, gamma, batch_size, process_group, save_dir,
+                     run_key=(lambda g: tuple(g.shape[-2:])) if resize else None)
 
 
 # ---- folder pairing (the one piece of host / disk code) ------------------------------------------------------------
@@ -412,6 +531,62 @@ def folder_pairs(low_dir: str, high_dir: str) -> FolderPairs:
     if skipped:
         warnings.warn(f"folder_pairs: no ground truth in {high_dir} for {len(skipped)} image(s): {', '.join(skipped)}")
     return FolderPairs(paths, kept, skipped)
+
+
+def _image_files(directory):
+    return sorted(f for f in os.listdir(directory)
+                  if os.path.isfile(os.path.join(directory, f)) and os.path.splitext(f)[1].lower() in _IMAGE_EXTENSIONS)
+
+
+def nested_folder_pairs(low_root: str, high_root: str, gt: str = "name") -> FolderPairs:
+    """The sets kept as one sub-folder per scene (measure_SID_blur.py): every sub-folder of low_root, in sorted order, and
+    in it every image file, sorted by name.  gt="name": the ground truth is the same file name in high_root/<sub>/ (LOL-Blur,
+    measure_SID_blur.py:89).  gt="first": every image of a sub-folder is paired with the first image file of
+    high_root/<sub>/ (SID, measure_SID_blur.py:85-87) -- the first of sorted(): the reference takes os.listdir's order, which
+    is not defined, and SID's label folders hold one file.  names are "<sub>/<file>" (evaluate(save_dir=) creates the
+    sub-folders); groups holds one (sub, [indices]) entry per sub-folder that has pairs; an image without a ground truth,
+    its whole sub-folder where high_root lacks it, is skipped and reported (a warning and .skipped) and counts in no average.
+    measure_SID_blur.py's PSNR omits the + 1e-8 of measure.py's; scoring keeps measure.py's (psnr())."""
+    if gt not in ("name", "first"):
+        raise ValueError(f"nested_folder_pairs: gt must be 'name' or 'first' (got {gt!r})")
+    paths, names, skipped, groups = [], [], [], []
+    for sub in sorted(d for d in os.listdir(low_root) if os.path.isdir(os.path.join(low_root, d))):
+        low_dir, high_dir = os.path.join(low_root, sub), os.path.join(high_root, sub)
+        labels = _image_files(high_dir) if os.path.isdir(high_dir) else []
+        members = []
+        for f in _image_files(low_dir):
+            label = (labels[0] if labels else None) if gt == "first" else (f if f in labels else None)
+            if label is None:
+                skipped.append(f"{sub}/{f}")
+                continue
+            members.append(len(paths))
+            paths.append((os.path.join(low_dir, f), os.path.join(high_dir, label)))
+            names.append(f"{sub}/{f}")
+        if members:
+            groups.append((sub, members))
+    if skipped:
+        warnings.warn(f"nested_folder_pairs: no ground truth under {high_root} for {len(skipped)} image(s): {', '.join(skipped)}")
+    pairs = FolderPairs(paths, names, skipped)
+    pairs.groups = groups
+    return pairs
+
+
+def group_means(result: EvalResult, pairs):
+    """-> ({sub: {"n": images, "psnr": mean, "ssim": ..., "psnr_gt_mean": ..., "ssim_gt_mean": ...}}, overall): the means of
+    each sub-folder of pairs.groups (nested_folder_pairs) over its images, and `overall`, the same keys over all of them --
+    the sum over every image divided by their number, which is what measure_SID_blur.py prints."""
+    per, total, n_all = {}, {k: 0.0 for k in _KEYS}, 0
+    for sub, members in pairs.groups:
+        sums = {k: 0.0 for k in _KEYS}
+        for k in _KEYS:
+            for i in members:
+                sums[k] += result.per_image[k][i]
+            total[k] += sums[k]
+        n_all += len(members)
+        per[sub] = {"n": len(members), **{k: sums[k] / len(members) for k in _KEYS}}
+    if n_all == 0:
+        raise ValueError("group_means: no images")
+    return per, {"n": n_all, **{k: total[k] / n_all for k in _KEYS}}
 
 
 # ---- NIQE (measure_niqe_bris.py -> loss/niqe_utils.py) -----------------------------------------------------------------

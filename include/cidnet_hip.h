@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 14
+#define CIDNET_ABI_VERSION 15
 
 int cidnet_abi_version(void);
 
@@ -536,6 +536,26 @@ int cidnet_metric_to_uint8(const float* x, uint8_t* q, int B, int Hp, int Wp, in
 long cidnet_metric_ws_floats(int B, int h, int w);
 int cidnet_metric_psnr_ssim(const uint8_t* restored, const uint8_t* gt, int gt_mean, double* psnr, double* ssim, float* ws,
                             long ws_floats, int B, int h, int w, void* stream);
+
+/* ---- Resize of the quantized output to the ground truth's size (measure.py:133-134, measure_SID_blur.py:91-92: im1 =
+ * im1.resize(im2.size), Pillow's default filter on an 8-bit RGB image: antialiased bicubic, a = -0.5, fixed point).  src
+ * (B,3,h_in,w_in) -> dst (B,3,h_out,w_out), planar uint8 on the device.  Per axis the caller supplies Pillow's tables for
+ * (n_in, n_out) as int32 device arrays (hvi-cidnet_amd/metrics.py: resize_plan): bounds (n_out,2) = first tap, tap count;
+ * coeffs (n_out,ksize) = the taps' coefficients scaled by 2^22, rows padded with zeros.  One pass writes
+ *   out = clamp((2^21 + sum_{k < count} in[first + k] * coeffs[o, k]) >> 22, 0, 255)   (int32 accumulator, arithmetic shift).
+ * The horizontal pass (bounds_x, coeffs_x, ksize_x: w_in -> w_out) runs first into tmp (B,3,h_in,w_out), then the vertical
+ * one (bounds_y, coeffs_y, ksize_y: h_in -> h_out) into dst; each rounds to uint8, so the order is part of the contract.  A
+ * pass whose axis keeps its size is skipped (its tables may be NULL, no rounding happens) and tmp is then unused (may be
+ * NULL); with both sizes kept dst receives a copy of src.  tmp: cidnet_metric_resize_ws_bytes(...) bytes (host only, launches
+ * nothing; 0 when at most one pass runs).  The tables live on the device and cannot be checked here without a copy: THEY MUST
+ * HOLD n_out ROWS OF ksize COEFFICIENTS; the kernels hold first and count inside the source axis and the row whatever a
+ * broken table says, so only bytes of src / tmp are ever read.  B * 3 * h * w >= 2^31 for src, dst or a needed tmp is
+ * CIDNET_ERR_SHAPE.  No atomics, no reductions: a byte depends on its own taps alone, bit-identical from call to call and
+ * independent of the rest of the batch. */
+long cidnet_metric_resize_ws_bytes(int B, int h_in, int w_in, int h_out, int w_out);
+int cidnet_metric_resize_u8(const uint8_t* src, uint8_t* dst, uint8_t* tmp, const int* bounds_x, const int* coeffs_x, int ksize_x,
+                            const int* bounds_y, const int* coeffs_y, int ksize_y, int B, int h_in, int w_in, int h_out,
+                            int w_out, void* stream);
 
 /* ---- NIQE features (measure_niqe_bris.py -> loss/niqe_utils.py: calculate_niqe with its defaults): the no-reference
  * score of the unpaired sets, per image up to its (blocks, 36) feature matrix; the 36 x 36 tail (nanmean, covariance,
