@@ -16,6 +16,12 @@
 // multiple of 4 reads and writes its 1-3 pixels one by one: no byte outside the crop window is ever touched, so a window that
 // ends at the arena's last byte (or starts at its first, mirrored) is safe.  No atomics, no reductions: a value depends on its
 // plan row alone.
+//
+// crop_flip_kernel<true> (cidnet_augment_crop_flip_raw) also writes the low image WITHOUT the power, raw = low / 255, which
+// the reference's train_tnsm.py:55,68 keeps beside `im1 ** gamma` for its noise-consistency term: the low image's bytes are
+// still loaded once per group, each byte is looked up in both tables, and a group issues three 16-byte stores --
+// 2 + 12 bytes per output pixel where two launches of the plain kernel move 2 * (2 + 8).  crop_flip_kernel<false> is the
+// plain kernel, instruction for instruction what it was before the template.
 #include "common.h"
 #include "cidnet_hip.h"
 
@@ -46,9 +52,11 @@ __device__ __forceinline__ void lookup_store(float* o, const float* tab, uint32_
   }
 }
 
+template <bool kRaw>
 __global__ __launch_bounds__(kThreads) void crop_flip_kernel(const uint8_t* __restrict__ arena, const long* __restrict__ plan,
                                                              const float* __restrict__ table, float* __restrict__ x,
-                                                             float* __restrict__ gt, int Sh, int Sw, int G) {
+                                                             float* __restrict__ gt, int Sh, int Sw, int G,
+                                                             float* __restrict__ raw) {
   __shared__ float tq[256], tx[256];
   {
     const float q = (float)threadIdx.x / 255.0f;
@@ -95,8 +103,22 @@ __global__ __launch_bounds__(kThreads) void crop_flip_kernel(const uint8_t* __re
       b[k] = __builtin_bswap32(b[k]) >> (8 * (4 - n[k]));
     }
     lookup_store(ox + dst[k], tx, a[k], n[k]);
+    if constexpr (kRaw) lookup_store(raw + (long)plane * Sh * Sw + dst[k], tq, a[k], n[k]);
     lookup_store(og + dst[k], tq, b[k], n[k]);
   }
+}
+
+template <bool kRaw>
+int launch_crop_flip(const uint8_t* arena, const long* plan, const float* table, float* x, float* raw, float* gt, int B, int Sh,
+                     int Sw, void* stream) {
+  const long G = ((long)Sw + 3) / 4;
+  const long items = (long)Sh * G;
+  if ((long)B * 3 > 65535 || items > (1L << 30)) return CIDNET_ERR_SHAPE;
+  const dim3 grid((unsigned)((items + kThreads * kGroups - 1) / (kThreads * kGroups)), (unsigned)(B * 3));
+  hipLaunchKernelGGL(crop_flip_kernel<kRaw>, grid, dim3(kThreads), 0, (hipStream_t)stream, arena, plan, table, x, gt, Sh, Sw,
+                     (int)G, raw);
+  CIDNET_LAUNCH_STATUS();
+  return CIDNET_OK;
 }
 
 }  // namespace
@@ -109,13 +131,13 @@ extern "C" {
 int cidnet_augment_crop_flip(const uint8_t* arena, const long* plan, const float* table, float* x, float* gt, int B, int Sh,
                              int Sw, void* stream) {
   CIDNET_CHECK_ARG(arena && plan && x && gt && B > 0 && Sh > 0 && Sw > 0);
-  const long G = ((long)Sw + 3) / 4;
-  const long items = (long)Sh * G;
-  if ((long)B * 3 > 65535 || items > (1L << 30)) return CIDNET_ERR_SHAPE;
-  const dim3 grid((unsigned)((items + kThreads * kGroups - 1) / (kThreads * kGroups)), (unsigned)(B * 3));
-  hipLaunchKernelGGL(crop_flip_kernel, grid, dim3(kThreads), 0, (hipStream_t)stream, arena, plan, table, x, gt, Sh, Sw, (int)G);
-  CIDNET_LAUNCH_STATUS();
-  return CIDNET_OK;
+  return launch_crop_flip<false>(arena, plan, table, x, nullptr, gt, B, Sh, Sw, stream);
+}
+
+int cidnet_augment_crop_flip_raw(const uint8_t* arena, const long* plan, const float* table, float* x, float* raw, float* gt,
+                                 int B, int Sh, int Sw, void* stream) {
+  CIDNET_CHECK_ARG(arena && plan && x && raw && gt && B > 0 && Sh > 0 && Sw > 0);
+  return launch_crop_flip<true>(arena, plan, table, x, raw, gt, B, Sh, Sw, stream);
 }
 
 }  // extern "C"

@@ -27,6 +27,23 @@ Differences from the reference, none of which changes the distribution of a batc
   * low image and ground truth share crop origin and flips by construction (the reference reseeds between its two
     transform calls to get exactly that);
   * with several ranks the permutation is padded by wrapping to world * ceil(N / world), as DistributedSampler does.
+
+The sets kept as one sub-folder per scene (data/SICE_blur_SID.py: LOLBlurDatasetFromFolder, SIDDatasetFromFolder,
+SICEDatasetFromFolder) train from the same arena:
+
+    pairs = ResidentPairs.from_scene_folders(low_root, high_root, device, gt="label")      # "name" LOL-Blur, "first" SID
+    batches = TrainBatches(pairs, batch_size=8, crop=256, gamma=(60, 120), sampling="scene")
+
+scene_pairs() pairs the files (a scene's label is decoded and stored once), scene_epoch_plan() draws every sample in the
+reference's two stages -- a scene uniformly, then one of its images uniformly, independently and with replacement -- and
+returns an ordinary EpochPlan, so the rows and the launch are the ones above.  An epoch has `samples` draws, by default the
+number of low images in the scenes, where the reference hard-codes 10200 / 2099 / 4803; every rank draws the same list and
+takes every world-th entry.
+
+TrainBatches(raw=True) yields (x, gt, raw): raw is the low image WITHOUT the power, which train_tnsm.py:55,68 keeps for the
+noise-consistency term of its loss while the network is fed `im1 ** gamma` (dp.DataParallelTrainer.step(x, gt, raw_input=raw);
+fit.run_epoch passes it on).  With gamma on the three tensors come from one launch of cidnet_augment_crop_flip_raw, which
+reads the low image once; with gamma off raw IS x.
 """
 from __future__ import annotations
 
@@ -34,6 +51,7 @@ import concurrent.futures as cf
 import ctypes
 import math
 import os
+import warnings
 from dataclasses import dataclass
 
 import numpy as np
@@ -121,13 +139,68 @@ def _chw_u8(img) -> torch.Tensor:
     return t.contiguous()
 
 
+def check_groups(groups, count) -> list:
+    """-> [(sub, [int indices])]: the scenes of a set of `count` low images, validated (ValueError): every index in range, no
+    scene empty, every low image in at most one scene.  A low image in no scene is legal and is never drawn."""
+    out, owner = [], {}
+    for entry in groups:
+        sub, members = entry
+        members = [int(i) for i in members]
+        if not members:
+            raise ValueError(f"groups: scene '{sub}' is empty")
+        for i in members:
+            if not 0 <= i < count:
+                raise ValueError(f"groups: scene '{sub}' names image {i}, outside the {count} low images of the set")
+            if i in owner:
+                raise ValueError(f"groups: image {i} is listed twice (scene '{owner[i]}' and scene '{sub}')")
+            owner[i] = sub
+        out.append((sub, members))
+    if not out:
+        raise ValueError("groups: no scene")
+    return out
+
+
+def scene_pairs(low_root: str, high_root: str, gt: str = "name") -> metrics.FolderPairs:
+    """The training sets kept as one sub-folder per scene (data/SICE_blur_SID.py) -> metrics.FolderPairs with names
+    "<sub>/<file>" and .groups = [(sub, [indices])], one entry per sub-folder that has pairs.  gt="name" (LOL-Blur: the same
+    file name in high_root/<sub>/) and gt="first" (SID: the first image file of high_root/<sub>/) are
+    metrics.nested_folder_pairs; gt="label" (SICE) pairs every image of low_root/<sub>/ with the file high_root/<sub><ext>,
+    <ext> the first of metrics.GT_EXTENSIONS that exists.  A scene without a label is skipped and reported as
+    nested_folder_pairs reports its skips (a warning and .skipped)."""
+    if gt in ("name", "first"):
+        return metrics.nested_folder_pairs(low_root, high_root, gt=gt)
+    if gt != "label":
+        raise ValueError(f"scene_pairs: gt must be 'name', 'first' or 'label' (got {gt!r})")
+    paths, names, skipped, groups = [], [], [], []
+    for sub in sorted(d for d in os.listdir(low_root) if os.path.isdir(os.path.join(low_root, d))):
+        low_dir = os.path.join(low_root, sub)
+        label = next((p for p in (os.path.join(high_root, sub + e) for e in metrics.GT_EXTENSIONS) if os.path.isfile(p)), None)
+        members = []
+        for f in metrics._image_files(low_dir):
+            if label is None:
+                skipped.append(f"{sub}/{f}")
+                continue
+            members.append(len(paths))
+            paths.append((os.path.join(low_dir, f), label))
+            names.append(f"{sub}/{f}")
+        if members:
+            groups.append((sub, members))
+    if skipped:
+        warnings.warn(f"scene_pairs: no ground truth under {high_root} for {len(skipped)} image(s): {', '.join(skipped)}")
+    pairs = metrics.FolderPairs(paths, names, skipped)
+    pairs.groups = groups
+    return pairs
+
+
 class ResidentPairs:
     """A paired training set on the device: one uint8 arena holding every image as planar (3,h,w), plus the host-side table
     of offsets and sizes (`layout`).  lows / highs: uint8 images, (h,w,3) arrays / PIL images or (3,h,w) tensors, of any
     sizes; gt_index[i] names the ground truth of low image i, so a label shared by many exposures is stored once.
-    max_bytes: refuse a larger set (default: a quarter of the device's memory)."""
+    max_bytes: refuse a larger set (default: a quarter of the device's memory).  groups: None, or the scenes of the set as
+    [(sub, [indices of its low images])] (what TrainBatches(sampling="scene") draws from): indices in range, no scene empty,
+    a low image in at most one scene, else ValueError."""
 
-    def __init__(self, lows, highs, device, gt_index=None, max_bytes=None, names=None):
+    def __init__(self, lows, highs, device, gt_index=None, max_bytes=None, names=None, groups=None):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError(_NO_CPU)
@@ -138,6 +211,7 @@ class ResidentPairs:
         if max_bytes is None:
             max_bytes = torch.cuda.get_device_properties(device).total_memory // 4
         self.names = list(names) if names is not None else None
+        self.groups = check_groups(groups, len(lows)) if groups is not None else None
         self.layout = arena_layout([t.shape[1:] for t in lows], [t.shape[1:] for t in highs], gt_index, max_bytes, self.names)
         self.device = device
         self.skipped = []
@@ -155,6 +229,23 @@ class ResidentPairs:
         fp = metrics.folder_pairs(low_dir, high_dir)
         if len(fp) == 0:
             raise ValueError(f"no image of {low_dir} has a ground truth in {high_dir}")
+        return cls._from_pairs(fp, device, max_bytes, threads)
+
+    @classmethod
+    def from_scene_folders(cls, low_root, high_root, device, gt="name", max_bytes=None, threads=16):
+        """The sets kept as one sub-folder per scene, paired by scene_pairs(low_root, high_root, gt) and decoded as
+        from_folders does; a ground truth shared by a scene (gt="first", gt="label") is decoded and stored once.  names are
+        "<sub>/<file>", `groups` the scenes (TrainBatches(sampling="scene")), `skipped` the low images without a ground
+        truth.  A low image whose size differs from its label's raises (arena_layout)."""
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(_NO_CPU)
+        fp = scene_pairs(low_root, high_root, gt)
+        if len(fp) == 0:
+            raise ValueError(f"no image under {low_root} has a ground truth under {high_root} (gt={gt!r})")
+        return cls._from_pairs(fp, device, max_bytes, threads, groups=fp.groups)
+
+    @classmethod
+    def _from_pairs(cls, fp, device, max_bytes, threads, groups=None):
         high_paths, slot, gt_index = [], {}, []
         for _, gp in fp.paths:
             if gp not in slot:
@@ -164,7 +255,7 @@ class ResidentPairs:
         with cf.ThreadPoolExecutor(max_workers=max(1, min(16, int(threads), os.cpu_count() or 1))) as ex:
             images = list(ex.map(metrics._read_rgb, [lp for lp, _ in fp.paths] + high_paths))
         n = len(fp.paths)
-        self = cls(images[:n], images[n:], device, gt_index=gt_index, max_bytes=max_bytes, names=fp.names)
+        self = cls(images[:n], images[n:], device, gt_index=gt_index, max_bytes=max_bytes, names=fp.names, groups=groups)
         self.skipped = list(fp.skipped)
         return self
 
@@ -246,6 +337,13 @@ def epoch_plan(sizes, crop, batch_size, seed=0, epoch=0, rank=0, world=1, shuffl
     per_rank = -(-n // world)
     total = per_rank * world
     padded = perm.repeat(-(-total // n))[:total]
+    return _rest_of_plan(g, padded, sizes, sh, sw, per_rank, rank, world, batch_size, drop_last, gamma)
+
+
+def _rest_of_plan(g, padded, sizes, sh, sw, per_rank, rank, world, batch_size, drop_last, gamma) -> EpochPlan:
+    """what follows the index list `padded` (world * per_rank samples, the same on every rank) in the generator's stream: crop
+    origins, flips, per-batch gammas; then rank's share"""
+    total = per_rank * world
     hw = torch.tensor(sizes, dtype=torch.int64)[padded]
     u = torch.rand((2, total), dtype=torch.float64, generator=g)
     span_y, span_x = hw[:, 0] - sh, hw[:, 1] - sw
@@ -266,6 +364,42 @@ def epoch_plan(sizes, crop, batch_size, seed=0, epoch=0, rank=0, world=1, shuffl
     last = batches[-1][1] if batches else 0
     return EpochPlan((sh, sw), padded[mine][:last].clone(), y0[mine][:last].clone(), x0[mine][:last].clone(),
                      flips[0][mine][:last].clone(), flips[1][mine][:last].clone(), batches, gammas)
+
+
+def scene_epoch_plan(groups, sizes, crop, batch_size, samples=None, seed=0, epoch=0, rank=0, world=1, drop_last=False,
+                     gamma=None, names=None) -> EpochPlan:
+    """One rank's epoch of a scene-folder set, drawn as data/SICE_blur_SID.py draws a sample: a scene uniformly over the
+    scenes, then one of its images uniformly, independently and with replacement.  groups: [(sub, [indices])]
+    (ResidentPairs.groups, scene_pairs().groups); sizes: (h, w) of every low image of the set.  samples: draws per epoch over
+    all ranks, default the number of low images in the scenes; world * ceil(samples / world) are drawn from one
+    torch.Generator seeded with (seed, epoch), the same list on every rank, and rank r takes positions r, r + world, ..., so
+    every rank runs the same number of steps with the same shapes.  Crop origins, flips, per-batch gammas, drop_last and the
+    error for an image smaller than the crop are epoch_plan's.  A pure function of its arguments."""
+    sh, sw = _crop_hw(crop)
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    world, rank, batch_size = int(world), int(rank), int(batch_size)
+    groups = check_groups(groups, len(sizes))
+    if batch_size <= 0 or world <= 0 or not 0 <= rank < world:
+        raise ValueError(f"scene_epoch_plan: batch_size {batch_size}, rank {rank}, world {world}")
+    samples = sum(len(m) for _, m in groups) if samples is None else int(samples)
+    if samples <= 0:
+        raise ValueError(f"scene_epoch_plan: samples must be positive (got {samples})")
+    for _, members in groups:
+        for i in members:
+            if sizes[i][0] < sh or sizes[i][1] < sw:
+                raise ValueError(f"image {_name(names, i)} is {sizes[i][0]} x {sizes[i][1]}, smaller than the {sh} x {sw} crop")
+    g = torch.Generator(device="cpu")
+    g.manual_seed(_epoch_seed(seed, epoch))
+    per_rank = -(-samples // world)
+    total = per_rank * world
+    count = torch.tensor([len(m) for _, m in groups], dtype=torch.int64)
+    start = torch.cumsum(count, 0) - count                       # where each scene's members begin in `flat`
+    flat = torch.tensor([i for _, m in groups for i in m], dtype=torch.int64)
+    scene = torch.randint(0, len(groups), (total,), generator=g)
+    k = count[scene]
+    member = torch.minimum((torch.rand(total, dtype=torch.float64, generator=g) * k.double()).floor().long(), k - 1)
+    padded = flat[start[scene] + member]
+    return _rest_of_plan(g, padded, sizes, sh, sw, per_rank, rank, world, batch_size, drop_last, gamma)
 
 
 def gamma_table(gamma: float) -> np.ndarray:
@@ -317,13 +451,19 @@ def _pack(rows: torch.Tensor, tables) -> torch.Tensor:
     return buf
 
 
-def _launch(pairs, buf_ptr, row, table_word, b, sh, sw):
-    """one batch: samples row .. row + b - 1 of the uploaded plan at buf_ptr; table_word: word offset of its table or None"""
+def _launch(pairs, buf_ptr, row, table_word, b, sh, sw, raw=False):
+    """one batch: samples row .. row + b - 1 of the uploaded plan at buf_ptr; table_word: word offset of its table or None.
+    raw: the launch that also writes the un-powered low image -> (x, gt, raw)"""
     x = torch.empty((b, 3, sh, sw), dtype=torch.float32, device=pairs.device)
     gt = torch.empty((b, 3, sh, sw), dtype=torch.float32, device=pairs.device)
-    lib().call("cidnet_augment_crop_flip", ops._p(pairs.arena), ctypes.c_void_p(buf_ptr + 8 * PLAN_WORDS * row),
-               ctypes.c_void_p(buf_ptr + 8 * table_word) if table_word is not None else None, ops._p(x), ops._p(gt), b, sh, sw,
-               ops._stream())
+    plan = ctypes.c_void_p(buf_ptr + 8 * PLAN_WORDS * row)
+    table = ctypes.c_void_p(buf_ptr + 8 * table_word) if table_word is not None else None
+    if raw:
+        r = torch.empty((b, 3, sh, sw), dtype=torch.float32, device=pairs.device)
+        lib().call("cidnet_augment_crop_flip_raw", ops._p(pairs.arena), plan, table, ops._p(x), ops._p(r), ops._p(gt), b, sh, sw,
+                   ops._stream())
+        return x, gt, r
+    lib().call("cidnet_augment_crop_flip", ops._p(pairs.arena), plan, table, ops._p(x), ops._p(gt), b, sh, sw, ops._stream())
     return x, gt
 
 
@@ -334,11 +474,12 @@ def _check_pairs(pairs):
         raise RuntimeError(_NO_CPU)
 
 
-def crop_flip(pairs: ResidentPairs, index, y0, x0, hflip, vflip, size, gamma: float = 1.0):
+def crop_flip(pairs: ResidentPairs, index, y0, x0, hflip, vflip, size, gamma: float = 1.0, raw: bool = False):
     """The batch kernel with explicit rows: sample k is the size = S | (S_h, S_w) window of pair index[k] at (y0[k], x0[k]),
     mirrored where hflip[k] / vflip[k] -> (x, gt), fp32 (B,3,S_h,S_w); x = (low / 255) ** gamma, gt = high / 255.  The rows
     (lists or CPU tensors) are checked on the host before anything is launched: ValueError for a window outside its image, an
-    index out of range or gamma <= 0."""
+    index out of range or gamma <= 0.  raw=True -> (x, gt, raw), raw = low / 255 without the power, all three from one launch
+    of cidnet_augment_crop_flip_raw (at gamma 1 without a table: x and raw are then the same values in two tensors)."""
     _check_pairs(pairs)
     sh, sw = _crop_hw(size)
     rows = plan_rows(pairs.layout, index, y0, x0, hflip, vflip, (sh, sw))
@@ -350,7 +491,7 @@ def crop_flip(pairs: ResidentPairs, index, y0, x0, hflip, vflip, size, gamma: fl
         raise ValueError(f"at most 21845 samples per launch (got {b})")
     with torch.cuda.device(pairs.device):
         buf = _pack(rows, tables).to(pairs.device)
-        return _launch(pairs, buf.data_ptr(), 0, b * PLAN_WORDS if tables else None, b, sh, sw)
+        return _launch(pairs, buf.data_ptr(), 0, b * PLAN_WORDS if tables else None, b, sh, sw, raw=bool(raw))
 
 
 class TrainBatches:
@@ -358,10 +499,23 @@ class TrainBatches:
     (epoch_plan), uploads it with one host-to-device copy and yields one batch per step, each from one kernel launch on the
     current stream into freshly allocated tensors (several steps may be in flight, so buffers are not recycled here).
     gamma: None, or (start, end) in hundredths as the reference's --start_gamma / --end_gamma.  With a process group (or an
-    initialised default group) every rank takes its share of the same permutation."""
+    initialised default group) every rank takes its share of the same permutation.
+    sampling: "permutation" (epoch_plan), or "scene" for a set with pairs.groups (scene_epoch_plan: a scene, then one of its
+    images, with replacement; `shuffle` has no meaning there); samples: draws per epoch of "scene" sampling over all ranks
+    (default: the number of low images in the scenes).  raw=True yields (x, gt, raw), raw being the low image without the
+    gamma power (train_tnsm.py:55,68): one launch of cidnet_augment_crop_flip_raw per batch with gamma on; with gamma off the
+    plain launch and raw is x itself, the same tensor."""
 
-    def __init__(self, pairs, batch_size, crop, seed=0, gamma=None, shuffle=True, drop_last=False, process_group=None):
+    def __init__(self, pairs, batch_size, crop, seed=0, gamma=None, shuffle=True, drop_last=False, process_group=None,
+                 sampling="permutation", samples=None, raw=False):
         _check_pairs(pairs)
+        if sampling not in ("permutation", "scene"):
+            raise ValueError(f"sampling must be 'permutation' or 'scene' (got {sampling!r})")
+        if sampling == "scene" and not getattr(pairs, "groups", None):
+            raise ValueError("sampling='scene' needs a set with scenes: ResidentPairs.from_scene_folders or ResidentPairs(groups=)")
+        if sampling == "permutation" and samples is not None:
+            raise ValueError("samples= belongs to sampling='scene': a permutation has the set's length")
+        self.sampling, self.samples, self.raw = sampling, None if samples is None else int(samples), bool(raw)
         self.pairs, self.batch_size, self.crop, self.seed = pairs, int(batch_size), _crop_hw(crop), int(seed)
         self.gamma, self.shuffle, self.drop_last = gamma, bool(shuffle), bool(drop_last)
         self.world, self.rank = 1, 0
@@ -375,12 +529,16 @@ class TrainBatches:
         return self._steps
 
     def plan(self, epoch) -> EpochPlan:
+        if self.sampling == "scene":
+            return scene_epoch_plan(self.pairs.groups, self.pairs.sizes, self.crop, self.batch_size, samples=self.samples,
+                                    seed=self.seed, epoch=epoch, rank=self.rank, world=self.world, drop_last=self.drop_last,
+                                    gamma=self.gamma, names=self.pairs.names)
         return epoch_plan(self.pairs.sizes, self.crop, self.batch_size, seed=self.seed, epoch=epoch, rank=self.rank,
                           world=self.world, shuffle=self.shuffle, drop_last=self.drop_last, gamma=self.gamma,
                           names=self.pairs.names)
 
     def epoch(self, epoch):
-        """generator of (x, gt), one per step of epoch `epoch`"""
+        """generator of (x, gt) -- (x, gt, raw) with raw=True --, one per step of epoch `epoch`"""
         p = self.plan(epoch)
         if not p.batches:
             return
@@ -393,5 +551,6 @@ class TrainBatches:
         ptr = buf.data_ptr()
         for k, (lo, hi) in enumerate(p.batches):
             with torch.cuda.device(self.pairs.device):
-                batch = _launch(self.pairs, ptr, lo, words + k * _TABLE_WORDS if tables else None, hi - lo, sh, sw)
-            yield batch
+                batch = _launch(self.pairs, ptr, lo, words + k * _TABLE_WORDS if tables else None, hi - lo, sh, sw,
+                                raw=self.raw and bool(tables))
+            yield (batch[0], batch[1], batch[0]) if self.raw and not tables else batch

@@ -257,6 +257,7 @@ class DataParallelTrainer:
         # issued from Python: at bs=8 about 5 ms of every 34 ms step are launch-bound phases (the 50x75 level)
         self.use_graph = use_graph
         self._graph = None
+        self._graw = None
         self._capturing = False
         # gradient arena and prepared-weight cache of this trainer (set up in _setup), installed for its passes only
         self._arena = None
@@ -264,7 +265,7 @@ class DataParallelTrainer:
         self.params = [p for p in model.parameters() if p.requires_grad]
 
     # ---- one-time setup: probe gradient order, flatten, hook -----------------------------------
-    def _setup(self, x, gt):
+    def _setup(self, x, gt, raw_input=None):
         # 1) probing backward: which parameters get gradients, in which order, and how often
         order, fired = [], {}
         hooks = []
@@ -283,7 +284,7 @@ class DataParallelTrainer:
                 st.acc, st.fwd, st.bwd, st.probe = False, 0, 0, [0, 0]
         self.model.zero_grad(set_to_none=True)
         with self._pass_scope():                    # no arena, no cache yet
-            loss = self._loss(self.model(x), gt, x)
+            loss = self._loss(self.model(x), gt, x, raw_input)
             loss.backward()
         for h in hooks:
             h.remove()
@@ -479,41 +480,49 @@ class DataParallelTrainer:
         from . import ops
         return ops.installed(self._arena, self._prep)
 
-    def _loss(self, out, gt, x):
+    def _check_raw(self, raw_input):
+        if raw_input is not None and not getattr(self.loss_fn, "wants_input", False):
+            raise ValueError("raw_input was given, but the loss function takes no input image (no true `wants_input` "
+                             "attribute, as losses.CIDNetLoss has): it would be dropped")
+
+    def _loss(self, out, gt, x, raw_input=None):
         """loss_fn(model(x), gt); a loss function with a true `wants_input` attribute (losses.CIDNetLoss: the TNSM noise terms
-        compare the output with the network input, train_tnsm.py:69) also gets the input as im1=x.  Tuple results of the
+        compare the output with the low image, train_tnsm.py:68-69) also gets im1: raw_input where the caller has one (the
+        low image before `** gamma`, as train_tnsm.py:55,68 keeps it), else the network input x.  Tuple results of the
         model (CIDNet_TNSM in train mode) are handed to the loss function as they are."""
         if getattr(self.loss_fn, "wants_input", False):
-            return self.loss_fn(out, gt, im1=x)
+            return self.loss_fn(out, gt, im1=raw_input if raw_input is not None else x)
         return self.loss_fn(out, gt)
 
-    def _fwd_bwd(self, x, gt):
+    def _fwd_bwd(self, x, gt, raw_input=None):
         with self._pass_scope():
             self._begin_pass(x)
-            loss = self._loss(self.model(x), gt, x)
+            loss = self._loss(self.model(x), gt, x, raw_input)
             self._backward(loss)
             self._end_pass()
         return loss
 
-    def _capture(self, x, gt):
-        """Static input buffers, two eager passes on the capture stream (scratch buffers reach their final size), then
+    def _capture(self, x, gt, raw_input=None):
+        """Static input buffers (the raw input's too, where the call has one), two eager passes on the capture stream
+        (scratch buffers reach their final size), then
         capture.  The side stream of the model and the weight-gradient stream fork from / join the capture stream
         exactly as in eager mode, so the graph keeps the three-stream concurrency.  Collectives and Adam stay outside
         (Adam's bias correction is a host scalar that changes every step)."""
         self._gx, self._ggt = x.clone(), gt.clone()
+        self._graw = raw_input.clone() if raw_input is not None else None
         st = torch.cuda.Stream(device=x.device)
         st.wait_stream(torch.cuda.current_stream())
         self._capturing = True
         try:
             with torch.cuda.stream(st):
                 for _ in range(2):
-                    self._fwd_bwd(self._gx, self._ggt)
+                    self._fwd_bwd(self._gx, self._ggt, self._graw)
                     self._join_wgrad_stream()
             torch.cuda.current_stream().wait_stream(st)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=st):
-                loss = self._fwd_bwd(self._gx, self._ggt)
+                loss = self._fwd_bwd(self._gx, self._ggt, self._graw)
                 self._join_wgrad_stream()
                 self._gloss = loss.detach()
             self._graph = g
@@ -521,7 +530,7 @@ class DataParallelTrainer:
         finally:
             self._capturing = False
 
-    def _graph_step(self, x, gt):
+    def _graph_step(self, x, gt, raw_input=None):
         # the graph reads the prepared operands' buffers: recapture once they were dropped, and re-prepare them when a
         # weight was written through torch since the last step (load_state_dict)
         if self._graph is not None and self._prep is not None:
@@ -529,10 +538,14 @@ class DataParallelTrainer:
                 self._graph = None
             elif self._prep.stale():
                 self._prep.refresh(self.flat_p.device)
+        if self._graph is not None and (raw_input is None) != (self._graw is None):
+            self._graph = None               # captured with / without a raw input: the loss reads another buffer
         if self._graph is None:
-            self._capture(x, gt)
+            self._capture(x, gt, raw_input)
         self._gx.copy_(x)
         self._ggt.copy_(gt)
+        if raw_input is not None:
+            self._graw.copy_(raw_input)
         self._graph.replay()
         if self.world > 1 or self._force_comm:
             dist.all_reduce(self.flat_g[:self.n_live], op=dist.ReduceOp.SUM, group=self.pg)
@@ -541,10 +554,13 @@ class DataParallelTrainer:
         return self._gloss
 
     # ---- the step ---------------------------------------------------------------------------------
-    def step(self, x, gt):
-        """forward, loss, backward (+ overlapped bucket all-reduce), fused Adam.  Returns the loss."""
+    def step(self, x, gt, raw_input=None):
+        """forward, loss, backward (+ overlapped bucket all-reduce), fused Adam.  Returns the loss.  raw_input: what a
+        `wants_input` loss function gets as im1 in place of x (the low image before the gamma power, train_tnsm.py:55,68;
+        data.TrainBatches(raw=True) yields it); ValueError with a loss function that takes no input."""
+        self._check_raw(raw_input)
         if not self._ready:
-            self._setup(x, gt)
+            self._setup(x, gt, raw_input)
         if x.is_cuda:
             while len(self._step_events) >= self.max_steps_in_flight:
                 self._step_events.pop(0).synchronize()
@@ -555,9 +571,9 @@ class DataParallelTrainer:
             while len(self._step_events) > 1 and self._queued_bytes(x.device) > self.max_queued_bytes:
                 self._step_events.pop(0).synchronize()
         if self.use_graph and x.is_cuda:
-            loss = self._graph_step(x, gt)
+            loss = self._graph_step(x, gt, raw_input)
         else:
-            loss = self._fwd_bwd(x, gt)
+            loss = self._fwd_bwd(x, gt, raw_input)
             for h in self._handles:
                 h.wait()
             self._join_wgrad_stream()
@@ -660,11 +676,12 @@ class DataParallelTrainer:
         st = torch.cuda.memory_stats_as_nested_dict(device)
         return st["active_bytes"]["all"]["current"] - st["allocated_bytes"]["all"]["current"]
 
-    def forward_backward(self, x, gt):
-        """forward + loss + backward only (gradients left in the flat arena); for timing splits."""
+    def forward_backward(self, x, gt, raw_input=None):
+        """forward + loss + backward only (gradients left in the flat arena); for timing splits.  raw_input: as step()."""
+        self._check_raw(raw_input)
         if not self._ready:
-            self._setup(x, gt)
-        loss = self._fwd_bwd(x, gt)
+            self._setup(x, gt, raw_input)
+        loss = self._fwd_bwd(x, gt, raw_input)
         for h in self._handles:
             h.wait()
         self._join_wgrad_stream()

@@ -21,9 +21,11 @@ What differs from the reference's loop:
     (`start_epoch` > 0: weights only, fresh Adam, restarted warm-up, shortened cosine period) is kept as it is;
   * left out: the per-epoch training/test.png dump of the step's own output (the validation's enhanced images can be written:
     val_args=dict(save_dir=...), metrics.evaluate), the metrics .md table (on_epoch hands the numbers to the caller), the
-    option parser, the cyclic scheduler variant, LPIPS (metrics.py), the two-stage TRAINING folder sampling of SICE / SID /
-    LOL-blur (evaluating those sets is there: val_args=dict(resize=True) for labels of another size, and
-    metrics.nested_folder_pairs for the one-sub-folder-per-scene layout of SID / LOL-blur).
+    option parser, the cyclic scheduler variant, LPIPS (metrics.py).
+The sets kept as one sub-folder per scene (SICE / SID / LOL-blur, data/SICE_blur_SID.py) train through the same loop:
+data.ResidentPairs.from_scene_folders and TrainBatches(sampling="scene") draw a scene, then one of its images; and a batch
+source that yields (x, gt, raw) -- TrainBatches(raw=True), the low image before `** gamma` -- has its third element handed to
+the step as raw_input, which is what train_tnsm.py:55,68 gives the TNSM loss.  fit() itself takes no argument for either.
 """
 from __future__ import annotations
 
@@ -42,8 +44,8 @@ _SCHEDULE_KEYS = ("nEpochs", "lr", "warmup_epochs", "start_warmup", "start_epoch
 def run_epoch(trainer, batches, epoch, step_log):
     """The steps of one epoch and ONE read of the step log -> its rows, (steps, 4) fp64 (dp.StepLog's columns)"""
     step_log.reset()
-    for x, gt in batches.epoch(epoch):
-        trainer.step(x, gt)
+    for batch in batches.epoch(epoch):                           # (x, gt) or (x, gt, raw): the third is the step's raw_input
+        trainer.step(*batch)
     return step_log.read()
 
 
@@ -73,7 +75,7 @@ def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, star
         process_group=None, on_epoch=None, trainer_args=None):
     """Train `model` for the epochs start_epoch + 1 ... start_epoch + nEpochs and return one record per epoch.
 
-    batches: anything with __len__ (steps per epoch) and epoch(e) yielding (x, gt): data.TrainBatches.
+    batches: anything with __len__ (steps per epoch) and epoch(e) yielding (x, gt) or (x, gt, raw): data.TrainBatches.
     The learning rate of the k-th epoch of this run (k = 0, 1, ...) is WarmupCosineLR(lr, nEpochs, warmup_epochs,
     start_epoch, start_warmup).lr_after(k): the reference constructs its scheduler, trains an epoch, then steps it, so with
     warm-up the first epoch runs at lr 0 (schedule.py lists the quirks); past the reference's single cosine period the

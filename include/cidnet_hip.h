@@ -608,6 +608,18 @@ int cidnet_metric_niqe_features(const uint8_t* rgb, const double* window, const 
 int cidnet_augment_crop_flip(const uint8_t* arena, const long* plan, const float* table, float* x, float* gt, int B, int Sh,
                              int Sw, void* stream);
 
+/* ---- The same batch with the un-powered low image beside it (train_tnsm.py:55,68 of the reference: the network is fed
+ * `im1 ** gamma`, the noise-consistency term of its loss is computed against the raw im1).  arena, plan, table, x, gt, the
+ * window arithmetic and the limits are exactly those of cidnet_augment_crop_flip; in addition
+ *   raw[s,c,i,j] = fp32(low[c,yy,xx]) / 255.0f, the same correctly rounded quotient as gt's, (B,3,Sh,Sw) fp32.
+ * table == NULL is allowed: x and raw then both receive the quotient.  The low image's bytes are read once and looked up in
+ * both tables: a launch moves B*3*Sh*Sw*(2 + 12) bytes, where two launches of the sibling (gamma on, gamma off) move
+ * B*3*Sh*Sw*(4 + 16).  Only bytes inside the crop windows are read, nothing outside the three (B,3,Sh,Sw) tensors is
+ * written; THE PLAN ROWS MUST HAVE BEEN RANGE-CHECKED ON THE HOST, as for the sibling.  B * 3 > 65535 is CIDNET_ERR_SHAPE.
+ * A value depends on its plan row alone: bit-identical from call to call and to what the sibling writes for the same row. */
+int cidnet_augment_crop_flip_raw(const uint8_t* arena, const long* plan, const float* table, float* x, float* raw, float* gt,
+                                 int B, int Sh, int Sw, void* stream);
+
 /* ---- Image files in and out (eval.py:60-75, eval_SID_blur.py, demo.py:40-60, app.py:33-53 of the reference: PIL image ->
  * ToTensor -> reflect pad to a multiple of 8 -> ** gamma -> model -> clamp -> crop -> ToPILImage -> save): the two conversions
  * between the interleaved (h,w,3) uint8 bytes of PIL / numpy / every file format and the planar fp32 (B,3,Hp,Wp) tensor of the

@@ -9,9 +9,15 @@
                  time per batch and kernel launches per batch
   train          DataParallelTrainer at B = 8, 400 x 600: fed one fixed batch (as bench.py does) and fed by TrainBatches with
                  crop (400, 600), alternated, three times each
+  raw            (--raw, a leg of its own) the launch that also writes the un-powered low image (cidnet_augment_crop_flip_raw:
+                 x, gt, raw) beside what gives the same three tensors without it -- two launches of the plain entry point,
+                 gamma on and gamma 1 -- and beside the plain single launch as it stands; same set, B and crops; the three
+                 alternate within one run, five rounds each, into preallocated outputs, timed by device events.  Bytes from
+                 shapes: B 3 S_h S_w (2 + 12) / 2 (2 + 8) / (2 + 8).  Lines are appended to profiles/data_raw.jsonl
   load           optional (--decode DIR): PNGs written to DIR, then ResidentPairs.from_folders timed (decode rate, load time)
 
     python tools/bench_data.py [--pairs 485] [--batches 200] [--train-steps 20] [--skip-train]
+    python tools/bench_data.py --raw [--batches 2000] [--out profiles/data_raw.jsonl]
     rocprofv3 --kernel-trace --stats -f csv -d OUT -o run -- python tools/bench_data.py --kernel-only
       (then: python tools/bench_data.py --share OUT/.../run_kernel_stats.csv -> time per launch of crop_flip_kernel and
        to_uint8_kernel, bytes per second, share of the HBM peak)
@@ -125,6 +131,66 @@ def _kernel_launches(fn):
                and not any(s in ev.name.lower() for s in ("memcpy", "memset")))
 
 
+def _raw_leg(a, dev, pairs):
+    """the --raw leg: one uploaded plan per crop, the same rows and table for the three variants"""
+    import ctypes
+    import torch
+    from hvi_cidnet_amd import data as D, ops
+    from hvi_cidnet_amd._lib import lib
+    n, rounds = a.batches, 5
+    lines = []
+    for size in CASES:
+        sh, sw = size
+        p = D.epoch_plan(pairs.sizes, size, B, seed=0, epoch=0, drop_last=True, gamma=(60, 120))
+        buf = D._pack(D.plan_rows(pairs.layout, p.index, p.y0, p.x0, p.hflip, p.vflip, p.crop),
+                      [D.gamma_table(g) for g in p.gammas]).to(dev)
+        words = p.index.numel() * D.PLAN_WORDS
+        steps = len(p.batches)
+        x, gt, raw, gt2 = (torch.empty((B, 3, sh, sw), dtype=torch.float32, device=dev) for _ in range(4))
+        arena, stream, k = ops._p(pairs.arena), ops._stream(), [0]
+
+        def args():
+            k[0] = (k[0] + 1) % steps
+            return (ctypes.c_void_p(buf.data_ptr() + 8 * D.PLAN_WORDS * B * k[0]),
+                    ctypes.c_void_p(buf.data_ptr() + 8 * (words + k[0] * D._TABLE_WORDS)))
+
+        def raw_launch():
+            plan, table = args()
+            lib().call("cidnet_augment_crop_flip_raw", arena, plan, table, ops._p(x), ops._p(raw), ops._p(gt), B, sh, sw, stream)
+
+        def two_launches():
+            plan, table = args()
+            lib().call("cidnet_augment_crop_flip", arena, plan, table, ops._p(x), ops._p(gt), B, sh, sw, stream)
+            lib().call("cidnet_augment_crop_flip", arena, plan, None, ops._p(raw), ops._p(gt2), B, sh, sw, stream)
+
+        def single_launch():
+            plan, table = args()
+            lib().call("cidnet_augment_crop_flip", arena, plan, table, ops._p(x), ops._p(gt), B, sh, sw, stream)
+        px = B * 3 * sh * sw
+        variants = [("raw_launch", raw_launch, px * 14), ("two_launches", two_launches, px * 20),
+                    ("single_launch", single_launch, px * 10)]
+        for _, fn, _ in variants:                            # warm-up: code objects, clocks
+            _events(fn, 50)
+        us = {name: [] for name, _, _ in variants}
+        for _ in range(rounds):
+            for name, fn, _ in variants:
+                us[name].append(_events(fn, n) * 1e3)
+        if a.kernel_only:
+            continue
+        for name, _, nb in variants:
+            v = sorted(us[name])
+            line = json.dumps({"what": "raw", "variant": name, "crop": list(size), "B": B, "launches_per_round": n,
+                               "rounds": rounds, "us_per_batch_median": v[rounds // 2], "us_per_batch_min": v[0],
+                               "us_per_batch_max": v[-1], "bytes": nb, "bytes_per_s_at_median": nb / (v[rounds // 2] * 1e-6),
+                               "timed": "device events around the launches of a round, host enqueue included"})
+            print(line)
+            lines.append(line)
+    if lines:                                                    # --kernel-only writes nothing and touches no file
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=485)
@@ -132,6 +198,8 @@ def main():
     ap.add_argument("--train-steps", type=int, default=20)
     ap.add_argument("--skip-train", action="store_true")
     ap.add_argument("--kernel-only", action="store_true", help="only launch the kernels (for a rocprofv3 run)")
+    ap.add_argument("--raw", action="store_true", help="only the leg that times cidnet_augment_crop_flip_raw")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "data_raw.jsonl"), help="--raw appends its lines here")
     ap.add_argument("--decode", default=None, help="directory to write PNGs to and load them back from")
     ap.add_argument("--share", default=None, help="kernel_stats.csv of a rocprofv3 run of this tool with --kernel-only")
     a = ap.parse_args()
@@ -145,6 +213,9 @@ def main():
     pairs, t_load = _resident(dev, a.pairs)
     print(json.dumps({"what": "resident_set", "pairs": a.pairs, "size": [H, W], "arena_bytes": pairs.arena.numel(),
                       "upload_s": t_load}))
+    if a.raw:
+        _raw_leg(a, dev, pairs)
+        return
     out = torch.rand((B, 3, H, W), device=dev)
     div = torch.full((), 255.0, dtype=torch.float32, device=dev)
 
