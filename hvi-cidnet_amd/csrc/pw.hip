@@ -16,6 +16,7 @@
 // dimension == 16 (mod 32) so the two k-rows of a 32-lane half hit disjoint banks.
 #include "common.h"
 #include "cidnet_hip.h"
+#include "pw_plan.h"
 
 namespace cidnet {
 namespace {
@@ -479,54 +480,206 @@ __global__ __launch_bounds__(kThreads, ((EPI == 2 && !(MT + LEFT <= 3 && KS == 9
   }
 }
 
-template <int MT, int EPI, int KS, class DT, int LEFT = 0>
-int launch_pw_rega(PwArgs a, int B, long nstream, hipStream_t s) {
-  constexpr int MB = 16 * MT + 4 * LEFT;
-  const long mblocks = (a.M + MB - 1) / MB;
-  // 512 blocks are resident (two per CU).  Store-heavy, bandwidth-bound layers (M >= 2K, below ~25 FLOP/B: e.g. the
-  // 36 -> 190 project_in at 200x300) run 15 % faster as about two rounds of shorter blocks; read-heavy and MFMA-bound
-  // ones prefer one round (tools/micro_pw.py target-blocks sweeps)
-  const bool store_heavy = a.M >= 2 * a.K && (long)a.M * a.K < 50L * (a.M + a.K);
-  const long target = g_pw_target_set ? g_pw_target_blocks : (store_heavy ? 1024 : 512);
-  long tpb = (nstream * mblocks * B + target - 1) / target;
+// ---------------------------------------------------------------------------------------------
+// Host-side launch plan of the forward kernels: every decision of the dispatch is taken here, once, by small functions;
+// the launchers below only map a plan to the kernel instantiation it names and take grid, tpb and LDS size from it, and
+// the query cidnet_pw_plan (kind 0) reports the same struct.
+// ---------------------------------------------------------------------------------------------
+struct PwPlan {
+  int path;              // 0 split-K, 1 register-resident, 2 LDS, 3 only the checked tail kernel (a ragged plane below one tile)
+  int launches;          // main launches: 2 for split-K with 384 < K <= 768, 0 for path 3, else 1
+  int MT, LEFT;          // channel tiles (and the 4-row group) of the main kernel; the tail kernel runs MT + LEFT tiles
+  int KS, KS2;           // k-steps held in registers: KS of the register kernel / KSW of the split-K launches (0: none)
+  int kc, nkc;           // LDS and tail kernels: K rows per staged chunk, chunks
+  int tpb;               // pixel tiles (split-K: 64-pixel groups) a block walks
+  long gx; int gy;       // grid of the main launch (z = B)
+  int gy_tail;           // grid.y of the tail launch (grid.x = 1)
+  int tail;              // 1: the plane's last tile goes through pw_conv_kernel<.., TAIL = true> in a launch of its own
+  int target;            // blocks the launch aimed for when it chose tpb
+  long lds;              // dynamic LDS bytes: split-K reduction buffer / weight panel chunk of the LDS and tail kernels
+  long ntiles, nstream;  // 256-pixel tiles of a plane; those the streaming kernels take
+};
+
+// Split-K (small planes, large K): 0 = not taken, else the number of launches.  Planes up to 8192 pixels (too few pixel
+// tiles to fill the chip otherwise), and up to 16384 when K is too deep for the LDS-resident weight panel (that kernel would
+// re-stage the panel for every pixel tile).  A wave can keep at most 24 k-steps x 3 channel tiles of weights in registers at
+// 2 waves/SIMD, i.e. K <= 384 per launch: larger K runs as two launches, the second accumulating into Y through the
+// residual epilogue -- which needs an f32 Y.
+inline int pw_splitk_launches(int K, long HW, int ydt) {
+  if (HW > 16384 || (HW > 8192 && K <= 320) || K < 64 || K > 768) return 0;
+  if (K > 384 && ydt != 0) return 0;
+  return K <= 384 ? 1 : 2;
+}
+
+inline int pw_splitk_ksw(int K) {                // k-steps per wave -> the instantiated register depth
+  const int ksw = (K + 15) / 16;
+  return ksw <= 9 ? 9 : (ksw <= 18 ? 18 : 24);
+}
+
+inline int pw_splitk_mt(int M) {
+  const int T = (M + 15) / 16;
+  return T >= 3 ? 3 : T;
+}
+
+// tiles (groups) a block walks so that about `target` blocks exist, at most 8; -> grid.x
+inline long pw_walk(long units, long mblocks, int B, long target, int* tpb_out) {
+  long tpb = (units * mblocks * B + target - 1) / target;
   tpb = tpb < 1 ? 1 : (tpb > 8 ? 8 : tpb);
-  a.tpb = (int)tpb;
+  *tpb_out = (int)tpb;
+  return (units + tpb - 1) / tpb;
+}
+
+// channel tiles per block of the register / LDS kernels
+inline int pw_pick_mt(int B, int M, int K, long HW) {
+  const int T = (M + 15) / 16;
+  const int ks = (K + 3) / 4;
+  int MT;
+  if (ks <= 24 && !(g_pw_dbg & 4)) {
+    // register-resident weights: at most 4 (ks <= 9) or 3 channel tiles per block.  Every block of output channels
+    // re-reads the whole input, so take the largest tile count that pads at most one tile in total
+    // (tools/sweep_pw.py: M=72 runs 88 us with 3+2(+1 padded) tiles, 120 us as five single-tile blocks)
+    const int mtmax = ks <= 9 ? 4 : 3;
+    int best = 1, best_pad = 1 << 30;
+    for (int mt = mtmax; mt >= 1; --mt) {        // least padding among those, the larger tile count on a tie (M = 36: 3, not 4)
+      const int pad = ((T + mt - 1) / mt) * mt;
+      if (pad <= T + 1 && pad < best_pad) { best = mt; best_pad = pad; }
+    }
+    MT = best;
+    // 65..80 output channels (the 36 -> 72 kv conv, the 72 x 72 attention maps): all five tiles in one block at one block per
+    // CU, so the input is read once instead of twice (3 + 2 tiles): 70 -> 60 us and 120 -> 85 us at 200x300.  Six tiles
+    // (95 / 190 channels) and four tiles at 18 k-steps spill and measured slower.
+    if (T == 5 && ks <= 18) MT = 5;
+    if (g_pw_force_mt >= 1 && g_pw_force_mt <= mtmax) MT = g_pw_force_mt;
+  } else {
+    int nblk = (T + 5) / 6;
+    MT = (T + nblk - 1) / nblk;
+    // small planes (e.g. 50x75): shrink the channel tile until ~512 blocks exist (never below 2 tiles)
+    const long ntiles = (HW + 255) / 256;
+    while (MT > 2 && ntiles * B * ((T + MT - 1) / MT) < 512) --MT;
+  }
+  return MT;
+}
+
+// The register-resident instantiation for a block of `mt` channel tiles, if one exists.  Register budget (2 waves/SIMD):
+// MT <= 4 with 9 k-steps, MT <= 3 with 18 or 24; MT = 5 (65..80 output channels in ONE block, one block per CU) with 9 or
+// 18 k-steps.
+struct PwRega { bool ok; int MT, LEFT, KS; };
+inline PwRega pw_rega_pick(int mt, int epi, int M, int K, int W, int zw) {
+  const int ks = (K + 3) / 4;
+  if (epi == 2 && ((W & 3) != 0 || zw < 4)) return {false, 0, 0, 0};   // its x2 epilogue wants a lane's four pixels in one row
+  // all output channels in one block and the last tile holds 1..4 of them (M = 36): 4-row group instead of a padded tile
+  if (mt >= 2 && mt <= 4) {
+    const int rem = M - 16 * (mt - 1);
+    if (M <= 16 * mt && rem >= 1 && rem <= 4 && !(g_pw_dbg & 32)) {
+      if (ks <= 9) return {true, mt - 1, 1, 9};
+      if (mt <= 3 && ks <= 18) return {true, mt - 1, 1, 18};
+      if (mt <= 3 && ks <= 24) return {true, mt - 1, 1, 24};
+    }
+  }
+  if (mt <= 5 && ks <= 9) return {true, mt, 0, 9};
+  if ((mt <= 3 || mt == 5) && ks <= 18) return {true, mt, 0, 18};
+  if (mt <= 3 && ks <= 24) return {true, mt, 0, 24};
+  return {false, 0, 0, 0};
+}
+
+// blocks the register kernel aims for: 512 are resident (two per CU).  Store-heavy, bandwidth-bound layers (M >= 2K, below
+// ~25 FLOP/B: e.g. the 36 -> 190 project_in at 200x300) run 15 % faster as about two rounds of shorter blocks; read-heavy
+// and MFMA-bound ones prefer one round (tools/micro_pw.py target-blocks sweeps)
+inline long pw_rega_target(int M, int K) {
+  const bool store_heavy = M >= 2 * K && (long)M * K < 50L * (M + K);
+  return g_pw_target_set ? g_pw_target_blocks : (store_heavy ? 1024 : 512);
+}
+
+// K rows of an MT-tile weight panel that fit 60 KB of LDS (leading dimension as in pw_conv_kernel)
+inline int pw_lds_ld(int mt) { return (mt % 2 == 0) ? 16 * mt + 16 : 16 * mt; }
+inline int pw_lds_kc(int mt, int K) {
+  const int kcmax = ((60 * 1024) / (pw_lds_ld(mt) * 4)) & ~3;
+  const int k4 = (K + 3) & ~3;
+  return k4 <= kcmax ? k4 : kcmax;
+}
+
+inline PwPlan pw_plan(int B, int M, int K, long HW, int W, int zw, int ydt, int epi) {
+  PwPlan p{};
+  p.ntiles = (HW + 255) / 256;
+  const int nl = (epi != 2 && !(g_pw_dbg & 16)) ? pw_splitk_launches(K, HW, ydt) : 0;
+  if (nl) {
+    p.path = 0; p.launches = nl;
+    p.MT = pw_splitk_mt(M);
+    p.KS = pw_splitk_ksw(nl == 2 ? 384 : K);
+    p.KS2 = nl == 2 ? pw_splitk_ksw(K - 384) : 0;
+    const long mblocks = (M + 16 * p.MT - 1) / (16 * p.MT);
+    // one round of the 512 resident blocks (was two): a block first gathers its weight fragments, and fewer, longer blocks
+    // amortise that -- 2.51 -> 2.32 ms per step over the coarse-level launches.  (Staging the panel through LDS in 128-k
+    // chunks instead of gathering it measured slower: 2.75 ms.)
+    p.target = 512;
+    p.gx = pw_walk((HW + 63) / 64, mblocks, B, p.target, &p.tpb);
+    p.gy = (int)mblocks;
+    p.lds = (long)4 * p.MT * 16 * 64 * sizeof(float);
+    return p;
+  }
+  const int mt = pw_pick_mt(B, M, K, HW);
+  p.kc = pw_lds_kc(mt, K);
+  p.nkc = (K + p.kc - 1) / p.kc;
+  p.lds = (long)p.kc * pw_lds_ld(mt) * sizeof(float);
+  const bool ragged = (HW % 4) != 0 || HW < 4;           // last tile needs the checked kernel
+  p.tail = ragged;
+  p.nstream = ragged ? p.ntiles - 1 : p.ntiles;
+  p.gy_tail = (M + 16 * mt - 1) / (16 * mt);
+  p.MT = mt; p.gy = p.gy_tail; p.tpb = 1; p.gx = 1;
+  p.target = (int)g_pw_target_blocks;
+  if (p.nstream == 0) { p.path = 3; return p; }
+  p.launches = 1;
+  const PwRega r = (g_pw_dbg & 4) ? PwRega{false, 0, 0, 0} : pw_rega_pick(mt, epi, M, K, W, zw);
+  if (r.ok) {
+    p.path = 1; p.MT = r.MT; p.LEFT = r.LEFT; p.KS = r.KS;
+    const int MB = 16 * r.MT + 4 * r.LEFT;
+    p.gy = (M + MB - 1) / MB;
+    p.target = (int)pw_rega_target(M, K);
+    p.gx = pw_walk(p.nstream, p.gy, B, p.target, &p.tpb);
+    return p;
+  }
+  p.path = 2;
+  if (K <= p.kc) p.gx = pw_walk(p.nstream, p.gy, B, p.target, &p.tpb);   // weights stay resident: walk several tiles
+  else p.gx = p.nstream;
+  return p;
+}
+
+template <int MT, int EPI, int KS, class DT, int LEFT = 0>
+int launch_pw_rega(PwArgs a, int B, const PwPlan& p, hipStream_t s) {
+  a.tpb = p.tpb;
   a.tile0 = 0;
-  a.ntile_lim = (int)nstream;
-  dim3 grid((unsigned)((nstream + tpb - 1) / tpb), (unsigned)mblocks, (unsigned)B);
+  a.ntile_lim = (int)p.nstream;
+  dim3 grid((unsigned)p.gx, (unsigned)p.gy, (unsigned)B);
   hipLaunchKernelGGL((pw_conv_rega_kernel<MT, EPI, KS, DT, LEFT>), grid, dim3(kThreads), 0, s, a);
   CIDNET_LAUNCH_STATUS();
   return CIDNET_OK;
 }
 
-// -> true if a register-resident instantiation exists for (MT, K); launches it.  Register budget
-// (2 waves/SIMD): MT <= 4 with 9 k-steps, MT <= 3 with 18 or 24; MT = 5 (65..80 output channels in ONE block, one block
-// per CU) with 9 or 18 k-steps.
+// the register-resident instantiation a plan of path 1 names (MT = the block's tiles as pw_pick_mt chose them; the plan's
+// own MT is one less where its LEFT group replaces the last tile)
 template <int MT, int EPI, class DT>
-bool try_rega(const PwArgs& a, int B, long nstream, hipStream_t s, int* rc) {
-  const int ks = (a.K + 3) / 4;
-  if (EPI == 2 && ((a.W & 3) != 0 || a.zw < 4)) return false;   // its x2 epilogue wants a lane's four pixels in one row
-  // all output channels in one block and the last tile holds 1..4 of them (M = 36): 4-row group instead of a padded tile
+int launch_pw_rega_of(const PwArgs& a, int B, const PwPlan& p, hipStream_t s) {
   if constexpr (MT >= 2 && MT <= 4) {
-    const int rem = a.M - 16 * (MT - 1);
-    if (a.M <= 16 * MT && rem >= 1 && rem <= 4 && !(a.dbg & 32)) {
-      if (ks <= 9) { *rc = launch_pw_rega<MT - 1, EPI, 9, DT, 1>(a, B, nstream, s); return true; }
+    if (p.LEFT == 1 && p.MT == MT - 1) {
+      if (p.KS == 9) return launch_pw_rega<MT - 1, EPI, 9, DT, 1>(a, B, p, s);
       if constexpr (MT <= 3) {
-        if (ks <= 18) { *rc = launch_pw_rega<MT - 1, EPI, 18, DT, 1>(a, B, nstream, s); return true; }
-        if (ks <= 24) { *rc = launch_pw_rega<MT - 1, EPI, 24, DT, 1>(a, B, nstream, s); return true; }
+        if (p.KS == 18) return launch_pw_rega<MT - 1, EPI, 18, DT, 1>(a, B, p, s);
+        if (p.KS == 24) return launch_pw_rega<MT - 1, EPI, 24, DT, 1>(a, B, p, s);
       }
     }
   }
-  if constexpr (MT <= 5) {
-    if (ks <= 9) { *rc = launch_pw_rega<MT, EPI, 9, DT>(a, B, nstream, s); return true; }
+  if (p.LEFT == 0 && p.MT == MT) {
+    if constexpr (MT <= 5) {
+      if (p.KS == 9) return launch_pw_rega<MT, EPI, 9, DT>(a, B, p, s);
+    }
+    if constexpr (MT <= 3 || MT == 5) {
+      if (p.KS == 18) return launch_pw_rega<MT, EPI, 18, DT>(a, B, p, s);
+    }
+    if constexpr (MT <= 3) {
+      if (p.KS == 24) return launch_pw_rega<MT, EPI, 24, DT>(a, B, p, s);
+    }
   }
-  if constexpr (MT <= 3 || MT == 5) {
-    if (ks <= 18) { *rc = launch_pw_rega<MT, EPI, 18, DT>(a, B, nstream, s); return true; }
-  }
-  if constexpr (MT <= 3) {
-    if (ks <= 24) { *rc = launch_pw_rega<MT, EPI, 24, DT>(a, B, nstream, s); return true; }
-  }
-  return false;
+  return CIDNET_ERR_SHAPE;                        // a plan that names no instantiated kernel (not reached)
 }
 
 // Split-K variant for small planes (e.g. 50x75 = 3750 pixels) with large K: too few 256-pixel tiles
@@ -614,149 +767,85 @@ __global__ __launch_bounds__(kThreads) void pw_conv_splitk_kernel(PwArgs a) {
 }
 
 template <int MT, int EPI, int KSW, class DT>
-int launch_pw_splitk(PwArgs a, int B, hipStream_t s) {
-  constexpr int MB = 16 * MT;
-  const long mblocks = (a.M + MB - 1) / MB;
-  const long ngroups = (a.HW + 63) / 64;
-  // one round of the 512 resident blocks (was two): a block first gathers its weight fragments, and fewer, longer blocks
-  // amortise that -- 2.51 -> 2.32 ms per step over the coarse-level launches.  (Staging the panel through LDS in 128-k
-  // chunks instead of gathering it measured slower: 2.75 ms.)
-  long tpb = (ngroups * mblocks * B + 511) / 512;
-  tpb = tpb < 1 ? 1 : (tpb > 8 ? 8 : tpb);
-  a.tpb = (int)tpb;
-  dim3 grid((unsigned)((ngroups + tpb - 1) / tpb), (unsigned)mblocks, (unsigned)B);
-  const size_t lds = (size_t)4 * MT * 16 * 64 * sizeof(float);
-  hipLaunchKernelGGL((pw_conv_splitk_kernel<MT, EPI, KSW, DT>), grid, dim3(kThreads), lds, s, a);
+int launch_pw_splitk(PwArgs a, int B, const PwPlan& p, hipStream_t s) {
+  a.tpb = p.tpb;
+  dim3 grid((unsigned)p.gx, (unsigned)p.gy, (unsigned)B);
+  hipLaunchKernelGGL((pw_conv_splitk_kernel<MT, EPI, KSW, DT>), grid, dim3(kThreads), (size_t)p.lds, s, a);
   CIDNET_LAUNCH_STATUS();
   return CIDNET_OK;
 }
 
-// small-plane / large-K dispatch; -> true if handled.  A wave can keep at most 24 k-steps x 3 channel
-// tiles of weights in registers at 2 waves/SIMD, i.e. K <= 384 per launch: larger K runs as two launches,
-// the second accumulating into Y through the residual epilogue.
+// one split-K launch with `ksw` k-steps per wave in registers (pw_splitk_ksw)
 template <int EPI, class DT>
-int splitk_one(const PwArgs& a, int B, hipStream_t s) {
-  const int ksw = (a.K + 15) / 16;               // k-steps per wave
-  const int T = (a.M + 15) / 16;
-  const int MT = T >= 3 ? 3 : T;
-#define SK(mt, kk) return launch_pw_splitk<mt, EPI, kk, DT>(a, B, s);
-  if (MT == 1) { if (ksw <= 9) SK(1, 9) if (ksw <= 18) SK(1, 18) SK(1, 24) }
-  if (MT == 2) { if (ksw <= 9) SK(2, 9) if (ksw <= 18) SK(2, 18) SK(2, 24) }
-  if (ksw <= 9) SK(3, 9) if (ksw <= 18) SK(3, 18) SK(3, 24)
+int splitk_one(const PwArgs& a, int B, const PwPlan& p, int ksw, hipStream_t s) {
+#define SK(mt, kk) return launch_pw_splitk<mt, EPI, kk, DT>(a, B, p, s);
+  if (p.MT == 1) { if (ksw == 9) SK(1, 9) if (ksw == 18) SK(1, 18) SK(1, 24) }
+  if (p.MT == 2) { if (ksw == 9) SK(2, 9) if (ksw == 18) SK(2, 18) SK(2, 24) }
+  if (ksw == 9) SK(3, 9) if (ksw == 18) SK(3, 18) SK(3, 24)
 #undef SK
 }
 
+// small-plane / large-K form (plan path 0): one launch, or two around K = 384
 template <int EPI, class DT>
-bool try_splitk(const PwArgs& a, int B, hipStream_t s, int* rc) {
-  // planes up to 8192 pixels (too few pixel tiles to fill the chip otherwise), and up to 16384 when K is too deep
-  // for the LDS-resident weight panel (that kernel would re-stage the panel for every pixel tile)
-  if (a.HW > 16384 || (a.HW > 8192 && a.K <= 320) || a.K < 64 || a.K > 768) return false;
-  if (a.K > 384 && a.ydt != 0) return false;     // the two-launch form accumulates through an f32 Y
-  if (a.K <= 384) { *rc = splitk_one<EPI, DT>(a, B, s); return true; }
+int launch_pw_splitk_plan(const PwArgs& a, int B, const PwPlan& p, hipStream_t s) {
+  if (p.launches == 1) return splitk_one<EPI, DT>(a, B, p, p.KS, s);
   PwArgs lo = a, hi = a;
   lo.K = 384;
-  *rc = splitk_one<EPI, DT>(lo, B, s);
-  if (*rc != CIDNET_OK) return true;
+  const int rc = splitk_one<EPI, DT>(lo, B, p, p.KS, s);
+  if (rc != CIDNET_OK) return rc;
   hi.K = a.K - 384;
   hi.X = a.xdt ? (const void*)((const bf16_t*)a.X + 384L * a.HW) : (const void*)((const float*)a.X + 384L * a.HW);
   hi.Wt = a.Wt + 384L * a.w_ks;
-  hi.R = (const float*)a.Y; hi.r_bs = a.y_bs;    // accumulate: Y += A[:, 384:] * X[384:]  (Y is f32 here, see below)
-  *rc = splitk_one<1, DT>(hi, B, s);
-  return true;
+  hi.R = (const float*)a.Y; hi.r_bs = a.y_bs;    // accumulate: Y += A[:, 384:] * X[384:]  (Y is f32 here, see pw_splitk_launches)
+  return splitk_one<1, DT>(hi, B, p, p.KS2, s);
 }
 
+// plan paths 1 .. 3 for a block of MT channel tiles
 template <int MT, int EPI, class DT>
-int launch_pw_epi(PwArgs a, int B, hipStream_t s) {
-  constexpr int MB = 16 * MT;
-  constexpr int ldA = (MT % 2 == 0) ? MB + 16 : MB;
-  const int kcmax = ((60 * 1024) / (ldA * 4)) & ~3;          // K rows that fit 60 KB of LDS
-  const int k4 = (a.K + 3) & ~3;
-  a.kc = k4 <= kcmax ? k4 : kcmax;
-  const size_t lds = (size_t)a.kc * ldA * sizeof(float);
-  const long ntiles = (a.HW + 255) / 256;
-  const long mblocks = (a.M + MB - 1) / MB;
-  const bool ragged = (a.HW % 4) != 0 || a.HW < 4;           // last tile needs the checked kernel
-  const long nstream = ragged ? ntiles - 1 : ntiles;
-  bool nstream_done = false;
-  if (nstream > 0 && !(g_pw_dbg & 4)) {
-    int rc = CIDNET_OK;
-    if (try_rega<MT, EPI, DT>(a, B, nstream, s, &rc)) {
-      if (rc != CIDNET_OK) return rc;
-      nstream_done = true;
-    }
-  }
-  if (nstream > 0 && !nstream_done) {
-    long tpb = 1;
-    if (a.K <= a.kc) {                                       // weights stay resident: walk several tiles
-      tpb = (nstream * mblocks * B + g_pw_target_blocks - 1) / g_pw_target_blocks;
-      tpb = tpb < 1 ? 1 : (tpb > 8 ? 8 : tpb);
-    }
-    a.tpb = (int)tpb;
+int launch_pw_epi(PwArgs a, int B, const PwPlan& p, hipStream_t s) {
+  a.kc = p.kc;
+  if (p.path == 1) {
+    const int rc = launch_pw_rega_of<MT, EPI, DT>(a, B, p, s);
+    if (rc != CIDNET_OK) return rc;
+  } else if (p.path == 2) {
+    a.tpb = p.tpb;
     a.tile0 = 0;
-    a.ntile_lim = (int)nstream;
-    dim3 grid((unsigned)((nstream + tpb - 1) / tpb), (unsigned)mblocks, (unsigned)B);
-    hipLaunchKernelGGL((pw_conv_kernel<MT, EPI, false, DT>), grid, dim3(kThreads), lds, s, a);
+    a.ntile_lim = (int)p.nstream;
+    dim3 grid((unsigned)p.gx, (unsigned)p.gy, (unsigned)B);
+    hipLaunchKernelGGL((pw_conv_kernel<MT, EPI, false, DT>), grid, dim3(kThreads), (size_t)p.lds, s, a);
     CIDNET_LAUNCH_STATUS();
   }
-  if (ragged) {
+  if (p.tail) {
     a.tpb = 1;
-    a.tile0 = (int)(ntiles - 1);
-    a.ntile_lim = (int)ntiles;
-    dim3 grid(1u, (unsigned)mblocks, (unsigned)B);
-    hipLaunchKernelGGL((pw_conv_kernel<MT, EPI, true, DT>), grid, dim3(kThreads), lds, s, a);
+    a.tile0 = (int)(p.ntiles - 1);
+    a.ntile_lim = (int)p.ntiles;
+    dim3 grid(1u, (unsigned)p.gy_tail, (unsigned)B);
+    hipLaunchKernelGGL((pw_conv_kernel<MT, EPI, true, DT>), grid, dim3(kThreads), (size_t)p.lds, s, a);
     CIDNET_LAUNCH_STATUS();
   }
   return CIDNET_OK;
 }
 
 template <int MT, class DT>
-int launch_pw(const PwArgs& a, int epi, int B, hipStream_t s) {
-  if (epi == 0) return launch_pw_epi<MT, 0, DT>(a, B, s);
-  if (epi == 1) return launch_pw_epi<MT, 1, DT>(a, B, s);
-  if constexpr (DT::X == 0 && DT::Y == 0) return launch_pw_epi<MT, 2, DT>(a, B, s);      // the upsample epilogue is fp32 only
+int launch_pw(const PwArgs& a, int epi, int B, const PwPlan& p, hipStream_t s) {
+  if (epi == 0) return launch_pw_epi<MT, 0, DT>(a, B, p, s);
+  if (epi == 1) return launch_pw_epi<MT, 1, DT>(a, B, p, s);
+  if constexpr (DT::X == 0 && DT::Y == 0) return launch_pw_epi<MT, 2, DT>(a, B, p, s);      // the upsample epilogue is fp32 only
   return CIDNET_ERR_SHAPE;
 }
 
 template <class DT>
 int dispatch_pw_dt(PwArgs a, int epi, int B, hipStream_t s) {
   a.dbg = g_pw_dbg;
-  if (epi != 2 && !(g_pw_dbg & 16)) {
-    int rc = CIDNET_OK;
-    if (epi == 0 ? try_splitk<0, DT>(a, B, s, &rc) : try_splitk<1, DT>(a, B, s, &rc)) return rc;
-  }
-  const int T = (a.M + 15) / 16;
-  const int ks = (a.K + 3) / 4;
-  int MT;
-  if (ks <= 24 && !(g_pw_dbg & 4)) {
-    // register-resident weights: at most 4 (ks <= 9) or 3 channel tiles per block.  Every block of output channels
-    // re-reads the whole input, so take the largest tile count that pads at most one tile in total
-    // (tools/sweep_pw.py: M=72 runs 88 us with 3+2(+1 padded) tiles, 120 us as five single-tile blocks)
-    const int mtmax = ks <= 9 ? 4 : 3;
-    int best = 1, best_pad = 1 << 30;
-    for (int mt = mtmax; mt >= 1; --mt) {        // least padding among those, the larger tile count on a tie (M = 36: 3, not 4)
-      const int pad = ((T + mt - 1) / mt) * mt;
-      if (pad <= T + 1 && pad < best_pad) { best = mt; best_pad = pad; }
-    }
-    MT = best;
-    // 65..80 output channels (the 36 -> 72 kv conv, the 72 x 72 attention maps): all five tiles in one block at one block per
-    // CU, so the input is read once instead of twice (3 + 2 tiles): 70 -> 60 us and 120 -> 85 us at 200x300.  Six tiles
-    // (95 / 190 channels) and four tiles at 18 k-steps spill and measured slower.
-    if (T == 5 && ks <= 18) MT = 5;
-    if (g_pw_force_mt >= 1 && g_pw_force_mt <= mtmax) MT = g_pw_force_mt;
-  } else {
-    int nblk = (T + 5) / 6;
-    MT = (T + nblk - 1) / nblk;
-    // small planes (e.g. 50x75): shrink the channel tile until ~512 blocks exist (never below 2 tiles)
-    const long ntiles = (a.HW + 255) / 256;
-    while (MT > 2 && ntiles * B * ((T + MT - 1) / MT) < 512) --MT;
-  }
-  switch (MT) {
-    case 1: return launch_pw<1, DT>(a, epi, B, s);
-    case 2: return launch_pw<2, DT>(a, epi, B, s);
-    case 3: return launch_pw<3, DT>(a, epi, B, s);
-    case 4: return launch_pw<4, DT>(a, epi, B, s);
-    case 5: return launch_pw<5, DT>(a, epi, B, s);
-    default: return launch_pw<6, DT>(a, epi, B, s);
+  const PwPlan p = pw_plan(B, a.M, a.K, a.HW, a.W, a.zw, a.ydt, epi);
+  if (p.path == 0) return epi == 0 ? launch_pw_splitk_plan<0, DT>(a, B, p, s) : launch_pw_splitk_plan<1, DT>(a, B, p, s);
+  switch (p.MT + p.LEFT) {
+    case 1: return launch_pw<1, DT>(a, epi, B, p, s);
+    case 2: return launch_pw<2, DT>(a, epi, B, p, s);
+    case 3: return launch_pw<3, DT>(a, epi, B, p, s);
+    case 4: return launch_pw<4, DT>(a, epi, B, p, s);
+    case 5: return launch_pw<5, DT>(a, epi, B, p, s);
+    default: return launch_pw<6, DT>(a, epi, B, p, s);
   }
 }
 
@@ -1023,6 +1112,23 @@ inline int wgrad_pch(int B, int M, int N, long HW) {
   return best;
 }
 
+// launch plan of the weight gradient, shared by the workspace size, the launcher and cidnet_pw_plan (kind 1)
+struct WgPlan {
+  int MT, NT, nmb, nnb;   // 16-row tiles of M / N per block, blocks along M / N
+  int pch, chunks, last;  // pixels per block, blocks along the plane, pixels of the last one
+};
+
+inline WgPlan wg_plan(int B, int M, int N, long HW) {
+  WgPlan p;
+  p.pch = wgrad_pch(B, M, N, HW);
+  p.chunks = (int)((HW + p.pch - 1) / p.pch);
+  p.last = (int)(HW - (long)(p.chunks - 1) * p.pch);
+  p.MT = pick_tiles(M, 3); p.NT = pick_tiles(N, 3);
+  p.nmb = ((M + 15) / 16 + p.MT - 1) / p.MT;
+  p.nnb = ((N + 15) / 16 + p.NT - 1) / p.NT;
+  return p;
+}
+
 }  // namespace
 }  // namespace cidnet
 
@@ -1068,9 +1174,8 @@ int cidnet_pw_conv_up_prelu(const float* X, long x_bs, const float* Wt, long w_m
 }
 
 long cidnet_pw_wgrad_ws_floats(int B, int M, int N, long HW) {
-  const int pch = wgrad_pch(B, M, N, HW);
-  const long chunks = (HW + pch - 1) / pch;
-  return (long)B * chunks * M * N;
+  const WgPlan p = wg_plan(B, M, N, HW);
+  return (long)B * p.chunks * M * N;
 }
 
 int cidnet_pw_wgrad_t(const void* dY, int dy_dt, long dy_bs, const void* X, int x_dt, long x_bs, float* dW, long dw_ld,
@@ -1087,13 +1192,12 @@ int cidnet_pw_wgrad_t(const void* dY, int dy_dt, long dy_bs, const void* X, int 
   if (ws_floats < cidnet_pw_wgrad_ws_floats(B, M, N, HW)) return CIDNET_ERR_WS;
   WgArgs a{};
   a.dY = dY; a.dy_bs = dy_bs; a.ddt = dy_dt; a.X = X; a.x_bs = x_bs; a.xdt = x_dt; a.slabs = ws; a.M = M; a.N = N; a.HW = HW;
-  a.pch = wgrad_pch(B, M, N, HW);
+  const WgPlan p = wg_plan(B, M, N, HW);
+  a.pch = p.pch;
   a.bf3 = (flags & CIDNET_WGRAD_FP32_MFMA) ? 0 : (flags & CIDNET_WGRAD_BF16_1LEVEL) ? 1 : 3;   // operand levels (0: fp32 MFMA)
   const int accumulate = flags & CIDNET_WGRAD_ACCUMULATE;
-  const int chunks = (int)((HW + a.pch - 1) / a.pch);
-  const int MT = pick_tiles(M, 3), NT = pick_tiles(N, 3);
-  const int nmb = ((M + 15) / 16 + MT - 1) / MT;
-  a.nnb = ((N + 15) / 16 + NT - 1) / NT;
+  const int chunks = p.chunks, MT = p.MT, NT = p.NT, nmb = p.nmb;
+  a.nnb = p.nnb;
   hipStream_t s = (hipStream_t)stream;
   int rc;
 #define WG_CASE(mt, nt) if (MT == mt && NT == nt) rc = launch_wg<mt, nt>(a, chunks, nmb, B, s); else
@@ -1107,6 +1211,34 @@ int cidnet_pw_wgrad_t(const void* dY, int dy_dt, long dy_bs, const void* X, int 
   hipLaunchKernelGGL(reduce_slabs_kernel, grid, dim3(256), 0, s, ws, n_red, M, N, dW, (long)M * dw_ld, dw_ld, accumulate);
   CIDNET_LAUNCH_STATUS();
   return CIDNET_OK;
+}
+
+/* host only: what the launchers of this file, of pwx.hip and of pwb.hip will do for a problem; see cidnet_hip.h */
+int cidnet_pw_plan(int kind, int B, int M, int K, long HW, int W, int zw, int x_dt, int y_dt, int epi, int* out, int n_out) {
+  static const int nfields[4] = {14, 9, 7, 5};
+  CIDNET_CHECK_ARG(out && kind >= 0 && kind <= 3 && n_out >= nfields[kind] && B > 0 && M > 0 && K > 0 && HW > 0);
+  int n = 0;
+  switch (kind) {
+    case 0: {   // cidnet_pw_conv_t (epi 0, 1: with R) / cidnet_pw_conv_up_prelu (epi 2: HW = 4 zh zw, W = 2 zw)
+      CIDNET_CHECK_ARG((x_dt | 1) == 1 && (y_dt | 1) == 1 && epi >= 0 && epi <= 2);
+      if (epi == 2) CIDNET_CHECK_ARG(zw > 0 && W == 2 * zw && HW % (2L * W) == 0);
+      if ((x_dt && y_dt) || (epi == 2 && (x_dt || y_dt))) return CIDNET_ERR_SHAPE;
+      const PwPlan p = pw_plan(B, M, K, HW, W, zw, y_dt, epi);
+      if (p.gx > 0x7fffffffL || p.lds > 0x7fffffffL) return CIDNET_ERR_SHAPE;
+      const int f[14] = {p.path, p.launches, p.MT, p.LEFT, p.KS, p.KS2, p.kc, p.nkc, p.tpb, (int)p.gx, p.gy, p.tail, p.target,
+                         (int)p.lds};
+      for (; n < 14; ++n) out[n] = f[n];
+      return CIDNET_OK;
+    }
+    case 1: {   // cidnet_pw_wgrad_t: dY has M planes, X has K
+      const WgPlan p = wg_plan(B, M, K, HW);
+      const int f[9] = {p.MT, p.NT, p.nmb, p.nnb, p.pch, p.chunks, p.last, B * p.chunks, p.chunks};
+      for (; n < 9; ++n) out[n] = f[n];
+      return CIDNET_OK;
+    }
+    case 2: return pwx_plan_fields(M, K, HW, out);
+    default: return pwb_plan_fields(B, M, K, HW, out);
+  }
 }
 
 }  // extern "C"

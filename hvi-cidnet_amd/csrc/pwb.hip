@@ -17,6 +17,7 @@
 //    slab per block at the end, a second kernel sums the slabs in fixed order (bitwise reproducible).
 // All LDS reads are compiler builtins (no inline assembly): the compiler places every wait.  No packed-fp32 / SDWA (build.py).
 #include "common.h"
+#include "pw_plan.h"
 
 namespace cidnet {
 namespace {
@@ -300,8 +301,10 @@ __global__ __launch_bounds__(256) void pwb_reduce_kernel(const float* __restrict
   }
 }
 
+inline long pwb_chunks(long HW) { return (HW + kBP - 1) / kBP; }   // 32-pixel chunks of a plane
+
 inline int pwb_blocks(int B, long HW) {
-  const long nch = (long)B * ((HW + kBP - 1) / kBP);
+  const long nch = (long)B * pwb_chunks(HW);
   return (int)(nch < kBMaxBlocks ? nch : kBMaxBlocks);
 }
 
@@ -326,7 +329,25 @@ inline bool pwb_shape(int M, int N, int& MT, int& NT) {
   return (MT == 12 && NT == 3) || (MT == 3 && NT == 6) || (MT == 3 && NT == 3) || (MT == 5 && NT == 3);
 }
 
+inline bool pwb_supported(int M, int N, long HW) {
+  int MT, NT;
+  return M > 0 && N > 0 && HW >= 4 && HW % 4 == 0 && pwb_shape(M, N, MT, NT);
+}
+
 }  // namespace
+
+// cidnet_pw_plan, kind 3 (pw.hip): the grid cidnet_pw_bwd_fused launches; block x walks chunks x, x + blocks, ...
+int pwb_plan_fields(int B, int M, int N, long HW, int* out) {
+  int MT, NT;
+  if (!pwb_supported(M, N, HW) || !pwb_shape(M, N, MT, NT)) return CIDNET_ERR_SHAPE;
+  const long chunks = pwb_chunks(HW);
+  if (chunks * B > 0x7fffffffL) return CIDNET_ERR_SHAPE;
+  const int nblk = pwb_blocks(B, HW);
+  const int f[5] = {MT, NT, (int)chunks, nblk, (int)((chunks * B + nblk - 1) / nblk)};
+  for (int n = 0; n < 5; ++n) out[n] = f[n];
+  return CIDNET_OK;
+}
+
 }  // namespace cidnet
 
 using namespace cidnet;
@@ -334,8 +355,7 @@ using namespace cidnet;
 extern "C" {
 
 int cidnet_pw_bwd_fused_supported(int M, int N, long HW) {
-  int MT, NT;
-  return M > 0 && N > 0 && HW >= 4 && HW % 4 == 0 && pwb_shape(M, N, MT, NT) ? 1 : 0;
+  return pwb_supported(M, N, HW) ? 1 : 0;
 }
 
 long cidnet_pw_bwd_fused_ws_floats(int B, int M, int N, long HW) {
@@ -351,7 +371,7 @@ int cidnet_pw_bwd_fused(const float* gY, long gy_bs, const float* X, long x_bs, 
   int MT, NT;
   if (!cidnet_pw_bwd_fused_supported(M, N, HW) || !pwb_shape(M, N, MT, NT)) return CIDNET_ERR_SHAPE;
   if (ws_floats < cidnet_pw_bwd_fused_ws_floats(B, M, N, HW)) return CIDNET_ERR_WS;
-  PwbArgs a{gY, gy_bs, X, x_bs, nullptr, gX, gx_bs, nullptr, B, M, N, HW, (int)((HW + kBP - 1) / kBP), 0};
+  PwbArgs a{gY, gy_bs, X, x_bs, nullptr, gX, gx_bs, nullptr, B, M, N, HW, (int)pwb_chunks(HW), 0};
   a.nchunks_all = B * a.chunks;
   hipStream_t s = (hipStream_t)stream;
   int nblk;

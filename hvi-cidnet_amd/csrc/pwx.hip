@@ -19,6 +19,7 @@
 // No packed-fp32 / SDWA instructions (hvi-cidnet_amd/build.py).
 #include "common.h"
 #include "cidnet_hip.h"
+#include "pw_plan.h"
 #include <type_traits>
 
 namespace cidnet {
@@ -390,6 +391,16 @@ int launch_pwx(const PwxArgs& a, const PwxPlan& p, int wl, int xl, int x_dt, int
 }
 
 }  // namespace
+
+// cidnet_pw_plan, kind 2 (pw.hip): the plan cidnet_pw_conv_bf16x3_pre_t launches
+int pwx_plan_fields(int M, int K, long HW, int* out) {
+  if (!cidnet_pw_conv_bf16x3_supported(M, K, HW)) return CIDNET_ERR_SHAPE;
+  const PwxPlan p = pwx_plan(M, K, HW);
+  const int f[7] = {p.cpg, p.KB, p.MT, p.WM, p.chunks, p.MTW, p.tiles_per_sample};
+  for (int n = 0; n < 7; ++n) out[n] = f[n];
+  return CIDNET_OK;
+}
+
 }  // namespace cidnet
 
 using namespace cidnet;

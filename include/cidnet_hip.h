@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 15
+#define CIDNET_ABI_VERSION 16
 
 int cidnet_abi_version(void);
 
@@ -198,6 +198,30 @@ int cidnet_pw_wgrad_t(const void* dY, int dy_dt, long dy_bs, const void* X, int 
 int cidnet_pw_wgrad(const float* dY, long dy_bs, const float* X, long x_bs, float* dW, long dw_ld,
                     int per_sample, int flags, float* ws, long ws_floats, int B, int M, int N,
                     long HW, void* stream);
+/* The launch plan the 1x1 convolution launchers take for a problem; host only, launches nothing and touches no device.
+ * Computed by the functions the launchers themselves call.  Writes the fields of `kind` to out[0..] (n_out >= 14 always
+ * suffices):
+ *  0  cidnet_pw_conv_t (epi 0; epi 1 with a residual R) and cidnet_pw_conv_up_prelu (epi 2: HW = 4 zh zw, W = 2 zw; W and zw
+ *     are read by epi 2 only) with x_dt -> y_dt tensors: path (0 split-K kernel, 1 register-resident kernel, 2 LDS kernel,
+ *     3 a ragged plane below one 256-pixel tile: only the checked tail kernel runs), main launches (2: split-K around
+ *     K = 384; 0 for path 3), MT, LEFT (a block owns 16 MT + 4 LEFT output channels; the tail kernel MT + LEFT tiles),
+ *     KS (k-steps in registers: KS of the register kernel, KSW of the first split-K launch; 0 otherwise), KS2 (KSW of the
+ *     second split-K launch), kc (K rows per staged weight chunk of the LDS and tail kernels; 0 for split-K), K chunks,
+ *     tpb (256-pixel tiles -- split-K: 64-pixel groups -- a block walks), grid x, grid y (grid z = B), tail (1: the
+ *     plane's last tile, HW % 4 != 0 or HW < 4, follows in a launch of the checked kernel), the block count tpb aimed for
+ *     (512 or 1024), dynamic LDS bytes (split-K: the reduction buffer; otherwise the weight chunk of the LDS / tail kernel)
+ *  1  cidnet_pw_wgrad_t (dY M planes, X K planes): MT, NT (16-row tiles per block), nmb, nnb (blocks along M, N), pch (pixels
+ *     per block), chunks (blocks along the plane), pixels of the last chunk, slabs summed per output without and with
+ *     per_sample (B chunks, chunks); workspace = B chunks M K floats
+ *  2  cidnet_pw_conv_bf16x3_pre_t: cpg (channels per lane group: 6 or 8; a k-block is 4 cpg channels), KB (k-blocks), MT
+ *     (16-row tiles of M), WM (waves of a block on one pixel group), chunks (grid y), MTW (tiles per wave), block pixel
+ *     tiles per sample (of 4 / WM x 64 pixels); prepared weights = KB MT 3 x 256 floats per set
+ *  3  cidnet_pw_bwd_fused (gY M planes, X K planes): MT, NT, 32-pixel chunks per sample, blocks, most chunks of one block
+ *     (block x walks chunks x, x + blocks, ... of the B samples' chunks)
+ * x_dt, y_dt and epi are read by kind 0 only.  CIDNET_ERR_SHAPE where the path does not take the problem (kind 0: bf16 ->
+ * bf16, epi 2 with a bf16 tensor; 2, 3: the *_supported predicates).  The tests assert through it that a case runs the
+ * path it is there for. */
+int cidnet_pw_plan(int kind, int B, int M, int K, long HW, int W, int zw, int x_dt, int y_dt, int epi, int* out, int n_out);
 
 /* ---- K5 / K8: depthwise 3x3 (zero pad) and the IEL gate  (net/LCA.py:14,16,53-55,62-65) --------
  * out = dw3x3(in) [+ addend]; channel c uses w1[c] if c < csplit else w2[c-csplit] (weights (.,1,3,3));

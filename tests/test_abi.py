@@ -217,6 +217,197 @@ def test_conv3x3_tiling_bad_arguments():
         assert q(kind, *shape, 3, out, n) == 0 and q(kind, *shape, 3, out, n - 1) == -1, kind
 
 
+_PW_FIELDS = (("path", "launches", "MT", "LEFT", "KS", "KS2", "kc", "nkc", "tpb", "gx", "gy", "tail", "target", "lds"),
+              ("MT", "NT", "nmb", "nnb", "pch", "chunks", "last", "n_red", "n_red_ps"),
+              ("cpg", "KB", "MT", "WM", "chunks", "MTW", "tiles"), ("MT", "NT", "chunks", "blocks", "most"))
+
+
+def _pw_plan(kind, B, M, K, HW, W=0, zw=0, xdt=0, ydt=0, epi=0):
+    """cidnet_pw_plan -> (status, {field: value}); the buffer is prefilled so that unwritten fields show"""
+    from hvi_cidnet_amd import _lib
+    out = (ctypes.c_int * 14)(*([-7] * 14))
+    rc = _lib.lib().raw("cidnet_pw_plan")(kind, B, M, K, HW, W, zw, xdt, ydt, epi, out, 14)
+    vals = list(out)
+    assert vals[len(_PW_FIELDS[kind]):] == [-7] * (14 - len(_PW_FIELDS[kind]))          # never past its own fields
+    if rc != 0:
+        assert vals == [-7] * 14                                                       # nothing written on an error
+    return rc, dict(zip(_PW_FIELDS[kind], vals))
+
+
+_PW_M = (1, 4, 5, 16, 17, 20, 32, 33, 36, 37, 48, 52, 64, 72, 80, 81, 95, 96, 100, 128, 144, 190, 382, 766)
+_PW_K = (1, 3, 4, 36, 37, 60, 63, 64, 72, 73, 96, 97, 100, 144, 190, 320, 321, 383, 384, 385, 400, 766, 768, 769, 772, 1000)
+_PW_HW = (1, 2, 3, 4, 5, 16, 61, 64, 255, 256, 257, 260, 1028, 3750, 8192, 8193, 8196, 15000, 16384, 16388, 60000, 240000, 921856)
+# (MT, LEFT) instantiated per register depth (pw.hip, launch_pw_rega_of)
+_PW_REGA = {9: {(1, 0), (2, 0), (3, 0), (4, 0), (5, 0), (1, 1), (2, 1), (3, 1)}, 18: {(1, 0), (2, 0), (3, 0), (5, 0), (1, 1), (2, 1)},
+            24: {(1, 0), (2, 0), (3, 0), (1, 1), (2, 1)}}
+
+
+def test_pw_plan_forward_contract():
+    """kind 0: the grid covers the pixel tiles (groups) and the output channels exactly once, the register kernel's (MT, LEFT,
+    KS) is an instantiated triple that holds all of K, a staged chunk fits 60 KB of LDS, the tail launch follows exactly for
+    ragged planes (the split-K kernel checks its own lanes), a ragged plane below one tile runs the tail kernel alone, split-K
+    takes two launches exactly for 384 < K <= 768 and never with a bf16 output, and the x2 epilogue never reaches split-K"""
+    seen, tpbs, targets = set(), set(), set()
+    for M in _PW_M:
+        for K in _PW_K:
+            for HW in _PW_HW:
+                for B in (1, 3, 8):
+                    for epi, xdt, ydt in ((0, 0, 0), (1, 0, 0), (0, 0, 1), (1, 1, 0), (2, 0, 0)):
+                        W, zw = 0, 0
+                        if epi == 2:
+                            if HW % 16 or HW > 240000:
+                                continue
+                            zw = 4 if HW % 80 else 5                 # both routes: W % 4 == 0 with zw >= 4, and W = 10
+                            W = 2 * zw
+                            if HW % (2 * W):
+                                continue
+                        rc, t = _pw_plan(0, B, M, K, HW, W, zw, xdt, ydt, epi)
+                        what = (B, M, K, HW, epi, xdt, ydt, t)
+                        assert rc == 0, what
+                        ragged = HW % 4 != 0 or HW < 4
+                        ntiles = -(-HW // 256)
+                        sk = t["path"] == 0
+                        assert sk == (epi != 2 and 64 <= K <= 768 and (HW <= 8192 or (HW <= 16384 and K > 320))
+                                      and not (K > 384 and ydt)), what
+                        units = -(-HW // 64) if sk else ntiles - ragged
+                        rows = 16 * t["MT"] + 4 * t["LEFT"]
+                        assert 1 <= t["tpb"] <= 8, what
+                        if t["path"] != 3:
+                            assert t["gx"] * t["tpb"] >= units > (t["gx"] - 1) * t["tpb"], what
+                            assert t["gy"] * rows >= M > (t["gy"] - 1) * rows, what
+                        assert t["tail"] == int(ragged and not sk), what
+                        assert (t["path"] == 3) == (ragged and HW < 256 and not sk), what
+                        assert t["target"] in (512, 1024), what
+                        if sk:
+                            assert t["launches"] == (2 if K > 384 else 1) and not (t["launches"] == 2 and ydt), what
+                            assert 1 <= t["MT"] <= 3 and t["LEFT"] == 0 and t["kc"] == 0 and t["nkc"] == 0, what
+                            k1 = min(K, 384)
+                            assert t["KS"] in (9, 18, 24) and 16 * t["KS"] >= k1 and (t["KS"] == 9 or 16 * (9 if t["KS"] == 18 else 18) < k1), what
+                            assert (t["KS2"] == 0) == (K <= 384) and (K <= 384 or (t["KS2"] in (9, 18, 24) and 16 * t["KS2"] >= K - 384)), what
+                            assert t["lds"] == 4 * t["MT"] * 16 * 64 * 4 <= 64 * 1024, what
+                            seen.add((0, t["MT"], t["KS"]))
+                            tpbs.add((0, t["tpb"]))
+                            continue
+                        assert t["launches"] == (0 if t["path"] == 3 else 1) and t["KS2"] == 0, what
+                        mt = t["MT"] + t["LEFT"]                     # tiles of the LDS / tail kernel
+                        lda = 16 * mt + (16 if mt % 2 == 0 else 0)
+                        assert 1 <= mt <= 6 and t["kc"] % 4 == 0 and t["kc"] * lda * 4 == t["lds"] <= 60 * 1024, what
+                        assert t["nkc"] == -(-K // t["kc"]) and (t["nkc"] == 1 or (t["kc"] + 4) * lda * 4 > 60 * 1024), what
+                        if t["path"] == 1:
+                            assert (t["MT"], t["LEFT"]) in _PW_REGA[t["KS"]] and 4 * t["KS"] >= K, what
+                            assert t["gy"] == 1 or t["LEFT"] == 0, what        # the 4-row group closes a single block
+                            assert epi != 2 or (W % 4 == 0 and zw >= 4), what
+                            assert t["target"] == (1024 if M >= 2 * K and M * K < 50 * (M + K) else 512), what
+                            targets.add(t["target"])
+                        else:
+                            assert t["LEFT"] == 0 and t["KS"] == 0 and t["target"] == 512, what
+                            if t["path"] == 2:
+                                assert K > 96 or (epi == 2 and (W % 4 != 0 or zw < 4)), what     # else a register kernel exists
+                                assert t["nkc"] == 1 or t["tpb"] == 1, what      # a re-staged panel: one tile per block
+                        seen.add((t["path"], t["MT"], t["LEFT"], t["KS"], min(t["nkc"], 2)))
+                        tpbs.add((t["path"], t["tpb"]))
+    assert {(0, mt, ks) for mt in (1, 2, 3) for ks in (9, 18, 24)} <= seen
+    assert {(1, mt, left, ks, 1) for ks, pairs in _PW_REGA.items() for mt, left in pairs} <= seen, \
+        {(1, mt, left, ks, 1) for ks, pairs in _PW_REGA.items() for mt, left in pairs} - seen
+    assert {(2, mt, 0, 0, n) for mt in range(1, 7) for n in (1, 2)} <= seen and {(3, 1, 0, 0, 1), (3, 1, 0, 0, 2), (3, 2, 0, 0, 1), (3, 2, 0, 0, 2), (3, 3, 0, 0, 1)} <= seen
+    assert {(p, n) for p in (0, 1, 2) for n in (1, 2, 8)} <= tpbs and targets == {512, 1024}
+
+
+def test_pw_plan_wgrad_contract():
+    """kind 1: blocks of a multiple of 128 pixels cover the plane exactly once, the tile blocks cover M and N, and the workspace
+    the fields imply is cidnet_pw_wgrad_ws_floats"""
+    from hvi_cidnet_amd import _lib
+    ws = _lib.lib().raw("cidnet_pw_wgrad_ws_floats")
+    pchs, tiles = set(), set()
+    for M in (1, 5, 16, 17, 36, 48, 49, 95, 190, 382):
+        for N in (1, 5, 16, 17, 36, 48, 72, 95, 190):
+            for B in (1, 3, 8):
+                for HW in (1, 12, 127, 128, 129, 512, 513, 1028, 3750, 15000, 20001, 40063, 60000, 240000):
+                    rc, t = _pw_plan(1, B, M, N, HW)
+                    what = (B, M, N, HW, t)
+                    assert rc == 0, what
+                    assert t["pch"] % 128 == 0 and 512 <= t["pch"] <= 4096, what
+                    assert t["chunks"] * t["pch"] >= HW > (t["chunks"] - 1) * t["pch"], what
+                    assert t["last"] == HW - (t["chunks"] - 1) * t["pch"] and 1 <= t["last"] <= t["pch"], what
+                    assert 1 <= t["MT"] <= 3 and 1 <= t["NT"] <= 3, what
+                    assert t["nmb"] * 16 * t["MT"] >= M > (t["nmb"] - 1) * 16 * t["MT"] - 15, what
+                    assert t["nnb"] * 16 * t["NT"] >= N > (t["nnb"] - 1) * 16 * t["NT"] - 15, what
+                    assert t["n_red"] == B * t["chunks"] and t["n_red_ps"] == t["chunks"], what
+                    assert ws(B, M, N, HW) == B * t["chunks"] * M * N, what
+                    pchs.add(t["pch"])
+                    tiles.add((t["MT"], t["NT"]))
+    assert tiles == {(a, b) for a in (1, 2, 3) for b in (1, 2, 3)} and len(pchs) >= 4 and 512 in pchs
+
+
+def test_pw_plan_bf16x3_and_fused_contract():
+    """kinds 2 and 3: the waves' tiles cover M with at most five per wave, the prepared-weight workspace the fields imply is
+    cidnet_pw_conv_bf16x3_ws_floats, the fused backward's persistent grid never exceeds 512 blocks and its rounds cover every
+    chunk, and the shape error agrees with the *_supported predicates"""
+    from hvi_cidnet_amd import _lib
+    L = _lib.lib()
+    ws = L.raw("cidnet_pw_conv_bf16x3_ws_floats")
+    layouts, cpgs = set(), set()
+    for M in (1, 16, 17, 32, 33, 36, 64, 80, 81, 96, 160, 161, 190, 320, 321, 336, 640, 766):
+        for K in (1, 23, 24, 25, 33, 36, 48, 49, 72, 95, 144, 766):
+            for HW in (1, 63, 64, 65, 127, 128, 130, 256, 257, 3750, 60000):
+                rc, t = _pw_plan(2, 2, M, K, HW)
+                what = (M, K, HW, t)
+                assert rc == (0 if L.raw("cidnet_pw_conv_bf16x3_supported")(M, K, HW) else -2), what
+                if rc:
+                    continue
+                assert t["cpg"] in (6, 8) and t["KB"] * 4 * t["cpg"] >= K > (t["KB"] - 1) * 4 * t["cpg"], what
+                assert t["cpg"] == 8 or -(-K // 24) == -(-K // 32), what       # 24-channel k-blocks only where they cost none
+                assert t["MT"] == -(-M // 16) and t["WM"] in (1, 2, 4) and 1 <= t["MTW"] <= 5, what
+                assert t["WM"] * t["chunks"] * t["MTW"] * 16 >= M, what
+                assert t["WM"] * t["chunks"] * (t["MTW"] - 1) < t["MT"], what   # no wave layer could go
+                px = (4 // t["WM"]) * 64
+                assert t["tiles"] * px >= HW > (t["tiles"] - 1) * px, what
+                for B, ps in ((1, 0), (3, 0), (3, 1)):
+                    assert ws(B, M, K, ps) == (B if ps else 1) * t["KB"] * t["MT"] * 3 * 256, what
+                layouts.add((t["WM"], t["MTW"], t["chunks"]))
+                cpgs.add(t["cpg"])
+    assert {(1, 2, 1), (1, 5, 1), (2, 3, 1), (2, 5, 1), (4, 3, 1), (4, 5, 1), (4, 3, 2), (4, 5, 2)} <= layouts and cpgs == {6, 8}
+    walks = set()
+    for M, N in ((190, 36), (181, 33), (36, 95), (36, 36), (72, 36), (36, 72), (190, 72), (16, 36), (96, 36)):
+        for B in (1, 2, 3, 8):
+            for HW in (1, 3, 4, 6, 32, 36, 260, 5508, 16384, 16420, 60000):
+                rc, t = _pw_plan(3, B, M, N, HW)
+                what = (B, M, N, HW, t)
+                assert rc == (0 if L.raw("cidnet_pw_bwd_fused_supported")(M, N, HW) else -2), what
+                if rc:
+                    assert L.raw("cidnet_pw_bwd_fused_ws_floats")(B, M, N, HW) == 0, what
+                    continue
+                assert (t["MT"], t["NT"]) == (-(-M // 16), -(-N // 16)), what
+                assert t["chunks"] * 32 >= HW > (t["chunks"] - 1) * 32, what
+                total = B * t["chunks"]
+                assert 1 <= t["blocks"] == min(total, 512), what
+                assert t["blocks"] * t["most"] >= total > t["blocks"] * (t["most"] - 1), what
+                kb = (t["MT"] + 1) // 2
+                assert L.raw("cidnet_pw_bwd_fused_ws_floats")(B, M, N, HW) == t["NT"] * kb * 3 * 256 + t["blocks"] * M * N, what
+                walks.add(min(t["most"], 3))
+    assert walks == {1, 2, 3}
+
+
+def test_pw_plan_bad_arguments():
+    from hvi_cidnet_amd import _lib
+    q = _lib.lib().raw("cidnet_pw_plan")
+    out = (ctypes.c_int * 14)()
+    ok = (1, 36, 36, 1028, 0, 0, 0, 0, 0)
+    assert q(0, *ok, out, 14) == 0
+    for bad in ((-1, *ok), (4, *ok), (0, 0, 36, 36, 1028, 0, 0, 0, 0, 0), (0, 1, 0, 36, 1028, 0, 0, 0, 0, 0), (1, 1, 36, -1, 1028, 0, 0, 0, 0, 0),
+                (2, 1, 36, 36, 0, 0, 0, 0, 0, 0), (0, 1, 36, 36, 1028, 0, 0, 2, 0, 0), (0, 1, 36, 36, 1028, 0, 0, 0, -1, 0),
+                (0, 1, 36, 36, 1028, 0, 0, 0, 0, 3), (0, 1, 36, 36, 1028, 0, 0, 0, 0, -1),
+                (0, 1, 36, 36, 1024, 16, 0, 0, 0, 2), (0, 1, 36, 36, 1024, 12, 8, 0, 0, 2), (0, 1, 36, 36, 1028, 16, 8, 0, 0, 2)):
+        assert q(*bad, out, 14) == -1, bad
+    assert q(0, 1, 36, 36, 1024, 16, 8, 0, 0, 2, out, 14) == 0
+    assert q(0, *ok, None, 14) == -1
+    for bad in ((0, 1, 36, 36, 1028, 0, 0, 1, 1, 0), (0, 1, 36, 36, 1024, 16, 8, 1, 0, 2), (0, 1, 36, 36, 1024, 16, 8, 0, 1, 2),
+                (2, 1, 16, 36, 1028, 0, 0, 0, 0, 0), (3, 1, 36, 36, 1026, 0, 0, 0, 0, 0), (3, 1, 40, 100, 1028, 0, 0, 0, 0, 0)):
+        assert q(*bad, out, 14) == -2, bad
+    for kind, n in enumerate((14, 9, 7, 5)):
+        assert q(kind, *ok, out, n) == 0 and q(kind, *ok, out, n - 1) == -1, kind
+
+
 def test_product_path_refuses_cpu_tensors():
     import torch
     from hvi_cidnet_amd.hvi_transform import RGB_HVI

@@ -34,10 +34,10 @@ def test_pw_conv_fwd_dgrad_wgrad(dev, B, Ci, Co, H, W):
     xd, wd, rd, gyd = (t.to(dev) for t in (x, w, r, gy))
     y = torch.empty_like(rd)
     ops.pw_conv(xd, 0, Ci * HW, wd, 0, 0, Ci, 1, y, 0, Co * HW, B, Co, Ci, HW, res=rd, r_bs=Co * HW)
-    close(y, F.conv2d(x, w) + r, what="fwd+res")
+    close(y, F.conv2d(x.double(), w.double()) + r.double(), what="fwd+res")          # references in fp64
     dx = torch.empty_like(xd)
     ops.pw_conv(gyd, 0, Co * HW, wd, 0, 0, 1, Ci, dx, 0, Ci * HW, B, Ci, Co, HW)
-    close(dx, F.conv_transpose2d(gy, w), what="dgrad")
+    close(dx, F.conv_transpose2d(gy.double(), w.double()), what="dgrad")
     gw = torch.empty_like(wd)
     ops.pw_wgrad(gyd, 0, Co * HW, xd, 0, Ci * HW, gw, 0, Ci, B, Co, Ci, HW)
     ref = torch.einsum("bmhw,bnhw->mn", gy.double(), x.double())
