@@ -19,8 +19,16 @@ The contract of the tiled mode is "the model applied to each window, blended by 
 is global (the gram matrix and the q / k norms run over all pixels of a sample), so a tiled result is NOT the whole-image
 result and nothing is claimed about their distance; the reference has no such mode.
 
-The kernels are csrc/imageio.hip (C ABI: cidnet_image_ingest / cidnet_image_egress and their _tiles forms, semantics in
-include/cidnet_hip.h).
+Geometric self-ensemble, opt-in (ensemble=1, the default everywhere, is the path above, untouched, with no new launch):
+    v = ensemble_views(x, first=0, count=4)        # fp32 (B,C,H,W) -> (B*4,C,H,W): views 0..3 (flips); first=4: (B*4,C,W,H)
+    y = ensemble_merge(ya, yb, na=4)               # the results mapped back, summed in view order, / (na + nb)
+    q = enhance_u8(model, img_u8, ensemble=8)      # 2: views {0,1}; 4: {0..3}; 8: all; the model runs once per view group
+    report = enhance_folder(model, in_dir, out_dir, ensemble=8)
+The contract is "the model applied to each view, mapped back, summed in a fixed order, divided by the count" (DESIGN.md 6.8);
+the reference has no such mode.  Not combined with tile=.
+
+The kernels are csrc/imageio.hip (C ABI: cidnet_image_ingest / cidnet_image_egress and their _tiles forms) and
+csrc/ensemble.hip (cidnet_ensemble_views / cidnet_ensemble_merge), semantics in include/cidnet_hip.h.
 
 enhance_folder is a pipeline; who owns what, and when:
   * decode workers (min(threads, 16)) read one file each through PIL's .convert('RGB') and write its bytes into a pinned
@@ -139,9 +147,91 @@ def egress(out: torch.Tensor, size=None) -> torch.Tensor:
     return q
 
 
-def _run(model, t, table):
-    """ingest -> model -> egress of a checked (B,h,w,3) batch; the caller holds the model's state (metrics._eval_state)"""
+# ---- self-ensemble: the dihedral views of the input, the model on each, the inverse-mapped results averaged -----------------
+_ENSEMBLE = {1: (1, 0), 2: (2, 0), 4: (4, 0), 8: (4, 4)}         # ensemble -> (na, nb): views 0 .. na - 1 and 4 .. 4 + nb - 1
+
+
+def _check_ensemble(ensemble, tile=None):
+    """-> (na, nb), or ValueError: ensemble is 1, 2, 4 or 8 (an int), and only 1 goes with tile="""
+    if isinstance(ensemble, bool) or not isinstance(ensemble, (int, np.integer)) or int(ensemble) not in _ENSEMBLE:
+        raise ValueError(f"ensemble must be 1, 2, 4 or 8 (got {ensemble!r})")
+    if int(ensemble) != 1 and tile is not None:
+        raise ValueError(f"ensemble={ensemble} with tile=: the self-ensemble runs on whole images only")
+    return _ENSEMBLE[int(ensemble)]
+
+
+def _planes(t, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise RuntimeError(f"{what}: expected an fp32 tensor (got {getattr(t, 'dtype', type(t).__name__)})")
+    if not t.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    if t.dim() != 4 or 0 in t.shape:
+        raise RuntimeError(f"{what}: expected (B,C,H,W), got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def ensemble_views(x: torch.Tensor, first: int, count: int) -> torch.Tensor:
+    """fp32 (B,C,H,W) on the device -> (B * count, C, Ho, Wo): views first .. first + count - 1 of every image, image b's view
+    first + v at index b * count + v.  View k in 0..7: if k & 1 reverse the columns, then if k & 2 reverse the rows, then if
+    k & 4 transpose -- torch's flip(-1), flip(-2), transpose(-1, -2), bit for bit, from one launch.  The range lies wholly in
+    0..3 ((Ho, Wo) = (H, W)) or wholly in 4..7 ((W, H)); anything else is a ValueError."""
+    if isinstance(x, torch.Tensor) and not x.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    x = _planes(x, "ensemble_views")
+    first, count = int(first), int(count)
+    if count < 1 or first < 0 or first + count > 8 or (first < 4) != (first + count <= 4):
+        raise ValueError(f"ensemble_views: views {first} .. {first + count - 1} must lie inside 0..3 or inside 4..7")
+    B, C, H, W = x.shape
+    y = torch.empty((B * count, C, W, H) if first >= 4 else (B * count, C, H, W), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        lib().call("cidnet_ensemble_views", ops._p(x), ops._p(y), B, C, H, W, first, count, ops._stream())
+    return y
+
+
+def ensemble_merge(ya: torch.Tensor, yb: torch.Tensor = None, na: int = 4) -> torch.Tensor:
+    """ya fp32 (B * na, C, H, W): views 0 .. na - 1 of B images as ensemble_views lays them out (or the model's results for
+    them), na = 1..4 views per image; yb (B * nb, C, W, H): views 4 .. 4 + nb - 1, nb = 1..4 (taken from yb's batch), or None
+    -> (B,C,H,W): per element acc = the view-0 value, then acc += every further view's value at the inverse-mapped position
+    (the transpose undone first, then the flips), view number ascending (ya before yb), each one fp32 addition, then acc /
+    (na + nb), a correctly rounded fp32 division.  No clamp: NaN and infinity propagate.  One launch."""
+    for t in (ya, yb):
+        if isinstance(t, torch.Tensor) and not t.is_cuda:
+            raise RuntimeError(_NO_CPU)
+    ya = _planes(ya, "ensemble_merge")
+    na = int(na)
+    if not 1 <= na <= 4 or ya.shape[0] % na:
+        raise ValueError(f"ensemble_merge: na = {na} must be 1..4 and divide ya's batch of {ya.shape[0]}")
+    B, (_, C, H, W), nb = ya.shape[0] // na, ya.shape, 0
+    if yb is not None:
+        yb = _planes(yb, "ensemble_merge")
+        nb = yb.shape[0] // B
+        if tuple(yb.shape) != (B * nb, C, W, H) or not 1 <= nb <= 4 or yb.device != ya.device:
+            raise ValueError(f"ensemble_merge: yb {tuple(yb.shape)} does not hold 1..4 transposed views of each of the {B} images "
+                             f"of ya {tuple(ya.shape)}")
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=ya.device)
+    with torch.cuda.device(ya.device):
+        lib().call("cidnet_ensemble_merge", ops._p(ya), na, ops._p(yb), nb, ops._p(out), B, C, H, W, ops._stream())
+    return out
+
+
+def _first(out):
+    return out[0] if isinstance(out, tuple) else out             # CIDNet_TNSM: (rgb, noise map or None)
+
+
+def _ensemble(fn, x, na, nb):
+    """fn (the model, or a stage of it) on the views of x, one call per group, merged: always two calls when nb > 0, square
+    image or not, so that an image's result does not depend on whether it happens to be square"""
+    ya = _first(fn(ensemble_views(x, 0, na)))
+    yb = _first(fn(ensemble_views(x, 4, nb))) if nb else None
+    return ensemble_merge(ya, yb, na)
+
+
+def _run(model, t, table, ensemble=(1, 0)):
+    """ingest -> model -> egress of a checked (B,h,w,3) batch; the caller holds the model's state (metrics._eval_state).
+    ensemble = (na, nb) other than (1, 0): ingest -> views -> model per group -> merge -> egress"""
     x, hw = _ingest(t, table)
+    if ensemble != (1, 0):
+        return egress(_ensemble(model, x, *ensemble), hw)
     out = model(x)
     if isinstance(out, tuple):                                   # CIDNet_TNSM: (rgb, noise map or None)
         out = out[0]
@@ -341,12 +431,17 @@ def _trans_attrs(gated, alpha_s, gated2, alpha):
 
 @torch.no_grad()
 def enhance_u8(model, images_u8: torch.Tensor, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3,
-               gated2: bool = False, alpha: float = 1.0, tile=None, overlap: int = 32, tile_batch: int = 8) -> torch.Tensor:
+               gated2: bool = False, alpha: float = 1.0, tile=None, overlap: int = 32, tile_batch: int = 8,
+               ensemble: int = 1) -> torch.Tensor:
     """uint8 (B,h,w,3) (or (h,w,3)) on the device -> the enhanced images, uint8 (B,h,w,3) on the device: ingest, the model in
     eval mode under no_grad with trans.gated / alpha_s / gated2 / alpha set (a tuple result -- CIDNet_TNSM -- gives its [0]),
     egress.  The model's attributes and the train / eval mode of every submodule are restored afterwards.
     tile = T or (Th, Tw): each image runs as tile_plan(h, w, tile, overlap) -> window ingest -> the model over the tiles in
-    chunks of tile_batch -> blended egress; NOT the whole-image result (module docstring).  tile=None: the whole image."""
+    chunks of tile_batch -> blended egress; NOT the whole-image result (module docstring).  tile=None: the whole image.
+    ensemble = 2, 4 or 8: geometric self-ensemble over views {0, 1}, {0..3} or {0..7} (ensemble_views) -- ingest, the views,
+    the model once per view group (0..3, then 4..7) on a batch of B * views, ensemble_merge, egress.  1: no view is built.
+    ValueError for any other value, and for ensemble != 1 together with tile=, before anything is launched."""
+    views = _check_ensemble(ensemble, tile)
     if isinstance(images_u8, torch.Tensor) and not images_u8.is_cuda:
         raise RuntimeError(_NO_CPU)
     t = _images_u8(images_u8, "enhance_u8")
@@ -357,7 +452,7 @@ def enhance_u8(model, images_u8: torch.Tensor, gamma: float = 1.0, gated: bool =
         with metrics._eval_state(model, _trans_attrs(gated, alpha_s, gated2, alpha)), torch.cuda.device(t.device):
             return torch.stack([_run_tiled(model, img, table, plan, tile_batch) for img in t])
     with metrics._eval_state(model, _trans_attrs(gated, alpha_s, gated2, alpha)), torch.cuda.device(t.device):
-        return _run(model, t, table)
+        return _run(model, t, table, views)
 
 
 # ---- the batching plan (pure host code) -------------------------------------------------------------------------------
@@ -461,12 +556,14 @@ class _Writer:
 class EnhanceReport:
     """What one rank's enhance_folder did: names / sizes (h, w) of its images in input order, batches (the input positions of
     each launch), seconds: {"wall": the call, "wait_for_slot": of it, the main thread waiting for a batch in flight to
-    finish so that its buffers come free}, tiles: with tile=, the number of tiles of each image (empty otherwise)"""
+    finish so that its buffers come free}, tiles: with tile=, the number of tiles of each image (empty otherwise), ensemble:
+    the number of views each image was averaged over (1: none were built)"""
     names: list = field(default_factory=list)
     sizes: list = field(default_factory=list)
     batches: list = field(default_factory=list)
     seconds: dict = field(default_factory=dict)
     tiles: list = field(default_factory=list)
+    ensemble: int = 1
 
 
 class _Stage:
@@ -495,7 +592,7 @@ def _decode(stop, path, name, stage):
 @torch.no_grad()
 def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
                    alpha: float = 1.0, batch_size: int = 1, threads: int = 8, depth: int = 2, process_group=None, tile=None,
-                   overlap: int = 32, tile_batch: int = 8) -> EnhanceReport:
+                   overlap: int = 32, tile_batch: int = 8, ensemble: int = 1) -> EnhanceReport:
     """eval.py / demo.py for a folder: every image file of in_dir (metrics.folder_images: its files and order) is enhanced as
     enhance_u8 does and saved to out_dir/<same file name> by PIL in the format its extension names (the reference's
     output_img.save(output_folder + name[0])); out_dir is created.  Decoding, the device and encoding overlap (module
@@ -505,7 +602,10 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
     and each rank reports its own images.  The first error of a worker stops the pipeline and is raised naming the file.
     The model's attributes and modes are restored afterwards.
     tile = T or (Th, Tw): every image is tiled on its own as enhance_u8(tile=, overlap=, tile_batch=) does, one image per
-    launch group (batch_size is ignored); the pipeline around it is the same.  report.tiles holds each image's tile count."""
+    launch group (batch_size is ignored); the pipeline around it is the same.  report.tiles holds each image's tile count.
+    ensemble = 2, 4 or 8: every batch is self-ensembled as enhance_u8(ensemble=) does (the model sees batches of batch_size *
+    views); ValueError for another value or together with tile=, before a worker starts."""
+    views = _check_ensemble(ensemble, tile)
     t_start = time.perf_counter()
     device = metrics._model_device(model)
     if device.type != "cuda":
@@ -522,7 +622,7 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
         batch_size, tile_batch = 1, _tile_batch(tile_batch)
     workers = max(1, min(int(threads), 16))
     mine = list(shard(len(files), rank, world))
-    report = EnhanceReport(names=[files.names[i] for i in mine])
+    report = EnhanceReport(names=[files.names[i] for i in mine], ensemble=int(ensemble))
     os.makedirs(out_dir, exist_ok=True)
     if not mine:
         report.seconds = {"wall": time.perf_counter() - t_start, "wait_for_slot": 0.0}
@@ -589,7 +689,7 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
                 uploaded.record(up)
                 torch.cuda.current_stream().wait_event(uploaded)
                 if plan is None:
-                    q = _run(model, t, table)
+                    q = _run(model, t, table, views)
                 else:
                     q = _run_tiled(model, t[0], table, plan, tile_batch).unsqueeze(0)
                     report.tiles.append(len(plan))

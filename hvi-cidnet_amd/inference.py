@@ -26,8 +26,13 @@ def pad_to_multiple(x, factor=8):
 
 
 @torch.no_grad()
-def enhance(model, img, gamma=1.0, alpha_s=1.0, alpha_i=1.0):
-    """img: (3,h,w) or (B,3,h,w) float in [0,1] on the model's device.  Returns the enhanced image(s), same shape."""
+def enhance(model, img, gamma=1.0, alpha_s=1.0, alpha_i=1.0, ensemble=1):
+    """img: (3,h,w) or (B,3,h,w) float in [0,1] on the model's device.  Returns the enhanced image(s), same shape.
+    ensemble = 2, 4 or 8: geometric self-ensemble over that many views of the padded input (image_io.ensemble_views /
+    ensemble_merge: the model once per view group, the results mapped back and averaged in a fixed order) before the clamp;
+    any other value but 1 is a ValueError."""
+    from . import image_io                           # image_io imports this module (through metrics)
+    views = image_io._check_ensemble(ensemble)
     squeeze = img.dim() == 3
     x = img.unsqueeze(0) if squeeze else img
     x, (h, w) = pad_to_multiple(x, 8)
@@ -35,7 +40,10 @@ def enhance(model, img, gamma=1.0, alpha_s=1.0, alpha_i=1.0):
     model.eval()
     model.trans.alpha_s = alpha_s
     model.trans.alpha = alpha_i
-    out = model(x ** gamma)
+    if ensemble != 1:
+        out = image_io._ensemble(model, (x ** gamma).float(), *views)
+    else:
+        out = model(x ** gamma)
     if isinstance(out, tuple):                       # CIDNet_TNSM returns (rgb, noise) in training mode only
         out = out[0]
     out = torch.clamp(out, 0, 1)[:, :, :h, :w]

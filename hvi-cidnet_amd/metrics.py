@@ -40,6 +40,7 @@ Differences from the reference scripts, none of which changes a per-image value:
 from __future__ import annotations
 
 import contextlib
+import functools
 import math
 import os
 import warnings
@@ -280,6 +281,7 @@ class EvalResult:
     names: list = field(default_factory=list)
     skipped: list = field(default_factory=list)       # low images without a ground truth (folder_pairs)
     resized: list = field(default_factory=list)       # indices of the pairs whose output was resized to the ground truth's size
+    ensemble: int = 1                                 # the number of views each output was averaged over (evaluate(ensemble=))
 
 
 _KEYS = ("psnr", "ssim", "psnr_gt_mean", "ssim_gt_mean")
@@ -344,13 +346,17 @@ def _plan(sizes, rank, world, batch_size):
 
 @torch.no_grad()
 def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, alpha, gamma, batch_size, process_group,
-              save_dir=None, run_key=None):
+              save_dir=None, run_key=None, ensemble=1):
     """The evaluation loop of evaluate() and evaluate_unpaired(), `who` / `noun` naming them in errors.  load(i, item, device)
     -> (input fp32 (3,h,w), what score needs of the image); trans_attrs: the model.trans attributes set for the run; score(q
     uint8 (B,3,h,w), [load's second values]) -> one (B,) fp64 device tensor per key; result(alpha=, per_image=, names=,
     <key>=mean ...) builds the result for one alpha.  save_dir: every scored image is also written there (image_io's egress
     kernel and writer), under items.names[i] or "<i as 5 digits>.png" (a name may hold sub-folders: they are created).
-    run_key(load's second value): what, beside the crop size, the samples of one score() call must share."""
+    run_key(load's second value): what, beside the crop size, the samples of one score() call must share.
+    ensemble: 1, or 2 / 4 / 8 -- the model runs on the views of the padded input, once per view group, and the merged fp32
+    result (image_io.ensemble_views / ensemble_merge) stands where the model's output stood."""
+    from . import image_io                                       # image_io imports this module
+    na, nb = image_io._check_ensemble(ensemble)
     device = _model_device(model)
     if not device.type == "cuda":
         raise RuntimeError(_NO_CPU)
@@ -372,7 +378,6 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
     loaded = []                # this rank's images not yet scored: (padded input, (h, w), load's second); _plan looks one ahead
     writer = None
     if save_dir is not None:
-        from . import image_io                                   # image_io imports this module
         os.makedirs(save_dir, exist_ok=True)
         file_names = getattr(items, "names", None)
         with torch.cuda.device(device):
@@ -391,10 +396,16 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
                 del loaded[:hi - lo]
                 x = torch.cat([b[0] for b in batch]) if len(batch) > 1 else batch[0][0]
                 xg = x ** gamma
-                trunk = model.trunk(xg) if use_trunk else None
+                if ensemble != 1:                                # one input per view group: views 0 .. na - 1, views 4 .. 4 + nb - 1
+                    groups = [image_io.ensemble_views(xg, 0, na)] + ([image_io.ensemble_views(xg, 4, nb)] if nb else [])
+                    trunks = [model.trunk(g) for g in groups] if use_trunk else None
+                trunk = model.trunk(xg) if use_trunk and ensemble == 1 else None
                 for ai, a in enumerate(alphas):
                     trans.alpha = a
-                    if trunk is not None:
+                    if ensemble != 1:                            # the trunk once per group, PHVIT per alpha and group, one merge
+                        outs = [trans.PHVIT_residual(*t) for t in trunks] if use_trunk else [image_io._first(model(g)) for g in groups]
+                        out = image_io.ensemble_merge(outs[0], outs[1] if nb else None, na)
+                    elif trunk is not None:
                         out = trans.PHVIT_residual(*trunk)
                     else:
                         out = model(xg)
@@ -436,7 +447,7 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
 
 
 def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
-             alpha=1.0, batch_size: int = 1, process_group=None, save_dir=None, resize: bool = False):
+             alpha=1.0, batch_size: int = 1, process_group=None, save_dir=None, resize: bool = False, ensemble: int = 1):
     """eval.py + measure.py on the device.  `pairs`: a sequence of (low, gt) -- low a (3,h,w) float image in [0, 1] (or a
     uint8 HWC image, converted as ToTensor() does), gt uint8 HWC / CHW or a float ToTensor() image of the same size
     (folder_pairs() yields these).  Each input is reflect-padded to a multiple of 8, run through model(pow(x, gamma)) in eval
@@ -457,6 +468,9 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     bicubic, byte for byte; per alpha of a sweep) and GT mean, PSNR and SSIM are taken from the resized image; the pairs'
     indices are reported in EvalResult.resized.  save_dir still receives the un-resized output, as eval.py writes it.  A
     ground truth smaller than 11 x 11 raises as ssim() does.
+    ensemble: 2, 4 or 8 -- geometric self-ensemble as image_io.enhance_u8(ensemble=) runs it: the model on the views of the
+    padded input, once per view group (with a sweep: the trunk once per group, PHVIT once per value and group), and the merged
+    fp32 result is what is quantized, saved and resized.  1: no view is built.  Any other value is a ValueError.
     The model's attributes and the train / eval mode of every submodule are restored afterwards."""
     def load(i, pair, device):
         x, g = _image_f32(pair[0], device), _gt_u8(pair[1], device)
@@ -480,11 +494,12 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     def result(per_image, **kw):
         flags = per_image.pop("resized", [])
         kw.pop("resized", None)
-        return EvalResult(skipped=skipped, per_image=per_image, resized=[i for i, f in enumerate(flags) if f], **kw)
+        return EvalResult(skipped=skipped, per_image=per_image, resized=[i for i, f in enumerate(flags) if f],
+                          ensemble=int(ensemble), **kw)
     return _evaluate("evaluate", "image pairs", model, pairs, load,
                      dict(gated=bool(gated), alpha_s=float(alpha_s), gated2=bool(gated2)), score,
                      _KEYS + ("resized",) if resize else _KEYS, result, alpha, gamma, batch_size, process_group, save_dir,
-                     run_key=(lambda g: tuple(g.shape[-2:])) if resize else None)
+                     run_key=(lambda g: tuple(g.shape[-2:])) if resize else None, ensemble=ensemble)
 
 
 # ---- folder pairing (the one piece of host / disk code) ------------------------------------------------------------
@@ -806,10 +821,11 @@ class UnpairedResult:
     niqe: float
     per_image: dict = field(default_factory=dict)     # "niqe" -> list, input order
     names: list = field(default_factory=list)
+    ensemble: int = 1                                 # the number of views each output was averaged over
 
 
 def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batch_size: int = 1, process_group=None,
-                      save_dir=None):
+                      save_dir=None, ensemble: int = 1):
     """eval.py --unpaired + measure_niqe_bris.py on the device.  `images`: a sequence of (3,h,w) float images in [0, 1] (or
     uint8 HWC images, converted as ToTensor() does; folder_images() yields these), each at least 96 x 96.  Each is reflect-
     padded to a multiple of 8, run through model(pow(x, gamma)) in eval mode under no_grad with trans.gated2 = True and
@@ -820,6 +836,7 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
     trunk runs once per batch, as in evaluate().  batch_size > 1 batches consecutive images of equal padded size.
     Data-parallel as evaluate(): rank r scores images i % world == r, one SUM all-reduce gathers the values.
     save_dir: as evaluate() -- the enhanced images are also written there, under images.names[i] or "<i as 5 digits>.png".
+    ensemble: as evaluate() -- 2, 4 or 8 views of the padded input, the merged result scored.
     The model's attributes and the train / eval mode of every submodule are restored afterwards.
     Not reproduced: BRISQUE; and the score is the quantized output's, not that of a lossy file decoded again (.jpg names)."""
     prm = _niqe_params(params)
@@ -831,7 +848,8 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
                              f"{NIQE_BLOCK} x {NIQE_BLOCK} pixels")
         return x, None
     return _evaluate("evaluate_unpaired", "images", model, images, load, dict(gated2=True), lambda q, _: (niqe(q, prm),),
-                     ("niqe",), UnpairedResult, alpha, gamma, batch_size, process_group, save_dir)
+                     ("niqe",), functools.partial(UnpairedResult, ensemble=int(ensemble)), alpha, gamma, batch_size, process_group,
+                     save_dir, ensemble=ensemble)
 
 
 class FolderImages:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 16
+#define CIDNET_ABI_VERSION 17
 
 int cidnet_abi_version(void);
 
@@ -690,6 +690,38 @@ int cidnet_image_ingest_tiles(const uint8_t* src, int h, int w, const float* tab
                               int tw, void* stream);
 int cidnet_image_egress_tiles(const float* tiles, const int* origins_y, int ny, const int* origins_x, int nx, const float* wy,
                               const float* wx, uint8_t* dst, int h, int w, int th, int tw, void* stream);
+
+/* ---- Geometric self-ensemble (hvi-cidnet_amd/image_io.py: ensemble_views / ensemble_merge): the 8 dihedral views of an image
+ * in front of the model and the mean of the inverse-mapped results behind it.  The reference has no such mode; the contract is
+ * "the model applied to each view, mapped back, summed in the fixed order below and divided by the number of views".
+ * View k in 0..7 of a plane X of shape (H, W) is built in this order: if k & 1 reverse the columns; then if k & 2 reverse the
+ * rows; then if k & 4 transpose.  With fr(i) = k & 2 ? H-1-i : i and fc(j) = k & 1 ? W-1-j : j:
+ *   k = 0..3 ("group A", shape (H, W)):  V_k[i, j] = X[fr(i), fc(j)]        for i < H, j < W
+ *   k = 4..7 ("group B", shape (W, H)):  V_k[p, q] = X[fr(q), fc(p)]        for p < W, q < H
+ * C is a plain batch-like dimension: every (b, c) plane is mapped alike.  Any H, W >= 1.
+ * views: x (B,C,H,W) -> y (B * count, C, Ho, Wo), (Ho, Wo) = (H, W) for group A and (W, H) for group B:
+ *   y[b * count + v, c] = V_{first + v}(x[b, c]) for v < count.  A pure permutation: every output value is bit for bit one
+ *   input value (NaN payloads and the sign of zero included), and exactly the B count C H W floats of y are written.  The views
+ *   first .. first + count - 1 must lie wholly inside 0..3 or wholly inside 4..7, so that all outputs share one shape.
+ *   CIDNET_ERR_SHAPE: count < 1; first < 0, first + count - 1 > 7, or a range that holds both 3 and 4; B * count > 65535; B, C,
+ *   H or W <= 0; more than 2^31 - 1 tiles of 64 x 64 per image (C * ceil(H / 64) * ceil(W / 64)).
+ * merge: ya (B * na, C, H, W) holds views 0 .. na - 1 of image b at index b * na + k; yb (B * nb, C, W, H) holds views 4 .. 4 +
+ *   nb - 1 at index b * nb + (k - 4) -- the layout views writes, or the model's output for it -> out (B,C,H,W).  The inverse of a
+ *   view undoes the transpose first and then the flips.  For every b, c, i < H, j < W, with fr / fc those of view k:
+ *     acc = ya[b * na, c, i, j]                                      (the view-0 value itself)
+ *     acc += ya[b * na + k, c, fr(i), fc(j)]        for k = 1 .. na - 1, ascending
+ *     acc += yb[b * nb + k - 4, c, fc(j), fr(i)]    for k = 4 .. 4 + nb - 1, ascending
+ *     out[b, c, i, j] = acc / (float)(na + nb)
+ *   every sum one fp32 addition, the quotient one correctly rounded fp32 division.  No clamp: NaN and infinity propagate
+ *   (cidnet_image_egress maps NaN to 0).  1 <= na <= 4 and 0 <= nb <= 4; yb is NULL exactly when nb == 0.
+ *   CIDNET_ERR_SHAPE: na < 1, na > 4, nb < 0, nb > 4; yb == NULL with nb > 0 or yb != NULL with nb == 0; B > 65535; B, C, H or
+ *   W <= 0; more than 2^31 - 1 tiles per image.
+ * Both: x / y / ya / out == NULL is CIDNET_ERR_ARG; nothing is written on an error.  No atomics and no reduction across
+ * lanes: a value depends on its own pixel's views alone, bit-identical from call to call and independent of the rest of the
+ * batch.  The transposed side goes through 64 x 64 tiles in LDS, so that every global access on either side is a run of
+ * consecutive floats (csrc/ensemble.hip). */
+int cidnet_ensemble_views(const float* x, float* y, int B, int C, int H, int W, int first, int count, void* stream);
+int cidnet_ensemble_merge(const float* ya, int na, const float* yb, int nb, float* out, int B, int C, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

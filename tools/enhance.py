@@ -5,10 +5,14 @@ bytes, encode, pipelined -- and is saved to --output_dir under its own name.  Pr
     python tools/enhance.py --input datasets/LOLdataset/eval15/low --output_dir output/LOLv1 --weight weights/LOLv1/w_perc.pth
     python tools/enhance.py --input photo.jpg --output_dir out --weight weights/generalization.safetensors --gamma 0.8 --alpha_s 1.1
     python tools/enhance.py --input photos/ --output_dir out --weight weights/generalization.safetensors --tile 1024
+    python tools/enhance.py --input photos/ --output_dir out --weight weights/generalization.safetensors --ensemble 8
 
 --tile N cuts every image into overlapping N x N windows, runs them through the model --tile_batch at a time and blends the
 overlaps: for images too large for one pass, or folders whose images all differ in size.  The model's channel attention is
 global, so a tiled result is not the whole-image result.
+--ensemble N (2, 4 or 8) is geometric self-ensemble: the model runs on N flipped / transposed views of every image and the
+results, mapped back, are averaged (2: the image and its mirror; 4: all flips; 8: the flips and their transposes).  N forwards
+per image; not combined with --tile.
 """
 import argparse
 import json
@@ -38,7 +42,10 @@ def main(argv=None):
     ap.add_argument("--tile", type=int, default=None, help="tile side, a multiple of 8 (default: the whole image in one pass)")
     ap.add_argument("--tile_overlap", type=int, default=32, help="pixels two neighbouring tiles share (at most half a tile)")
     ap.add_argument("--tile_batch", type=int, default=8, help="tiles per model launch")
+    ap.add_argument("--ensemble", type=int, choices=(1, 2, 4, 8), default=1, help="views averaged per image (default 1: none)")
     a = ap.parse_args(argv)
+    if a.ensemble != 1 and a.tile is not None:
+        ap.error("--ensemble and --tile cannot be combined")
     if not os.path.exists(a.input):
         ap.error(f"--input {a.input}: no such file or directory")
 
@@ -58,12 +65,12 @@ def main(argv=None):
         sys.exit(f"no image file (.png .jpg .bmp .JPG .jpeg) in {a.input}")
     rep = P.enhance_folder(model, files, a.output_dir, gamma=a.gamma, gated=a.gated, alpha_s=a.alpha_s, gated2=a.gated2,
                            alpha=a.alpha_i, batch_size=a.batch_size, threads=a.threads, depth=a.depth, tile=a.tile,
-                           overlap=a.tile_overlap, tile_batch=a.tile_batch)
+                           overlap=a.tile_overlap, tile_batch=a.tile_batch, ensemble=a.ensemble)
     wall = rep.seconds["wall"]
     print(json.dumps({"what": "enhance", "input": a.input, "output_dir": a.output_dir, "variant": a.variant, "images": len(rep.names),
                       "batches": len(rep.batches), "seconds": rep.seconds, "images_per_s": len(rep.names) / wall if wall > 0 else None,
                       "missing_keys": missing, "unexpected_keys": unexpected, "names": rep.names,
-                      "sizes": [list(s) for s in rep.sizes], "tile": a.tile, "tiles": rep.tiles}))
+                      "sizes": [list(s) for s in rep.sizes], "tile": a.tile, "tiles": rep.tiles, "ensemble": rep.ensemble}))
 
 
 if __name__ == "__main__":
