@@ -21,7 +21,14 @@ and, for the sets without ground truth (eval.py --unpaired + measure_niqe_bris.p
     res = M.evaluate_unpaired(model, images, prm, alpha=1.0, gamma=1.0, batch_size=1, save_dir=None)
     images = M.folder_images(dir)
 
-The kernels are csrc/metrics.hip, csrc/resize.hip and csrc/niqe.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
+and LOE, the lightness order error of the enhanced image against the low input (the reference has none: opt-in):
+
+    step, rows, cols = M.loe_grid(h, w, sample=50)
+    num, m = M.loe_counts(low_u8, q, sample=50)     # exact int64 pair counts (B,) on the device, and the sample count
+    v = M.loe(low_u8, q, sample=50)                 # (B,) float64 on the device: num / m (normalized=True: num / m^2)
+    res = M.evaluate_unpaired(model, images, prm, loe=True)     # res.loe, res.per_image["loe"]
+
+The kernels are csrc/metrics.hip, csrc/resize.hip, csrc/niqe.hip and csrc/loe.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
 Differences from the reference scripts, none of which changes a per-image value:
   * measure.py counts a low image without a ground truth in the divisor of its averages (it skips the image after
     `n += 1`); here such an image is skipped and reported (FolderPairs.skipped, EvalResult.skipped) and not counted;
@@ -814,18 +821,84 @@ def niqe(images: torch.Tensor, params) -> torch.Tensor:
     return torch.from_numpy(niqe_score(feat, params)).to(feat.device)
 
 
+# ---- LOE (Wang et al. 2013; no counterpart in the reference) -------------------------------------------------------------
+def loe_grid(h: int, w: int, sample=50):
+    """The sampling grid of LOE, pure host code -> (step, rows, cols): step = max(1, min(h, w) // sample) (1 when sample is
+    None: every pixel), rows = h // step, cols = w // step; sample (i, j) is source pixel (i * step, j * step)."""
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f"loe_grid: sizes must be positive (got {h} x {w})")
+    if sample is None:
+        step = 1
+    else:
+        if int(sample) < 1:
+            raise ValueError(f"loe_grid: sample must be positive or None (got {sample})")
+        step = max(1, min(h, w) // int(sample))
+    return step, h // step, w // step
+
+
+def _loe_input(low, out):
+    if not (isinstance(low, torch.Tensor) and isinstance(out, torch.Tensor)):
+        raise ValueError("loe: expected two tensors")
+    _on_device(low, out)
+    if low.dtype != torch.uint8 or out.dtype != torch.uint8:
+        raise ValueError(f"loe takes uint8 images (got {low.dtype}, {out.dtype}); see to_uint8")
+    for t, what in ((low, "low"), (out, "out")):
+        if t.dim() not in (3, 4) or t.shape[-3] != 3:
+            raise ValueError(f"loe: {what}: expected (B,3,h,w) or (3,h,w), got {tuple(t.shape)}")
+    a, b = _batched(low, "low"), _batched(out, "out")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"loe: low {tuple(a.shape)} and out {tuple(b.shape)} differ")
+    return a, b
+
+
+def _loe_launch(low, out, sample):
+    a, b = _loe_input(low, out)
+    B, _, h, w = a.shape
+    step, rows, cols = loe_grid(h, w, sample)
+    L = lib()
+    n = L.raw("cidnet_metric_loe_ws_bytes")(B)
+    ws = torch.empty(n, dtype=torch.uint8, device=a.device)
+    num = torch.empty(B, dtype=torch.int64, device=a.device)
+    val = torch.empty(B, dtype=torch.float64, device=a.device)
+    with torch.cuda.device(a.device):
+        L.call("cidnet_metric_loe_u8", ops._p(a), ops._p(b), B, h, w, step, ops._p(num), ops._p(val), ops._p(ws), n, ops._stream())
+    return num, val, rows * cols
+
+
+def loe_counts(low_u8: torch.Tensor, out_u8: torch.Tensor, sample=50):
+    """uint8 (B,3,h,w) (or (3,h,w)) pairs on the device -> (num int64 (B,) on the device, m): over the m = rows * cols samples
+    of loe_grid(h, w, sample), with L = max(R, G, B) of the low image and Le of the enhanced one, num counts the ordered pairs
+    (x, y), y = x included, whose order differs: (L(x) >= L(y)) != (Le(x) >= Le(y)).  Exact; no host synchronisation."""
+    num, _, m = _loe_launch(low_u8, out_u8, sample)
+    return num, m
+
+
+def loe(low_u8: torch.Tensor, out_u8: torch.Tensor, sample=50, normalized: bool = False) -> torch.Tensor:
+    """(B,) float64 on the device: num / m, the classic lightness order error (0 .. m), or num / m^2 (normalized=True, 0 .. 1);
+    see loe_counts.  Numbers compare only under the same sampler: sample=50 strides to about 50 samples on the short side,
+    sample=None takes every pixel."""
+    num, val, m = _loe_launch(low_u8, out_u8, sample)
+    if not normalized:
+        return val
+    # a true division: dividing by a host scalar on the device would multiply by fl(1 / m^2), one ulp off for some counts
+    return num.to(torch.float64) / torch.full((), float(m * m), dtype=torch.float64, device=num.device)
+
+
 @dataclass
 class UnpairedResult:
-    """Mean NIQE over the evaluated images (running sum in input order, divided by their number) and the per-image values"""
+    """Mean NIQE -- and mean LOE, where evaluate_unpaired(loe=True) asked for it, else NaN -- over the evaluated images (running
+    sum in input order, divided by their number) and the per-image values"""
     alpha: float
     niqe: float
-    per_image: dict = field(default_factory=dict)     # "niqe" -> list, input order
+    per_image: dict = field(default_factory=dict)     # "niqe" (and "loe") -> list, input order
     names: list = field(default_factory=list)
     ensemble: int = 1                                 # the number of views each output was averaged over
+    loe: float = math.nan                             # mean lightness order error against the inputs as supplied
 
 
 def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batch_size: int = 1, process_group=None,
-                      save_dir=None, ensemble: int = 1):
+                      save_dir=None, ensemble: int = 1, loe: bool = False, loe_sample=50):
     """eval.py --unpaired + measure_niqe_bris.py on the device.  `images`: a sequence of (3,h,w) float images in [0, 1] (or
     uint8 HWC images, converted as ToTensor() does; folder_images() yields these), each at least 96 x 96.  Each is reflect-
     padded to a multiple of 8, run through model(pow(x, gamma)) in eval mode under no_grad with trans.gated2 = True and
@@ -837,8 +910,12 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
     Data-parallel as evaluate(): rank r scores images i % world == r, one SUM all-reduce gathers the values.
     save_dir: as evaluate() -- the enhanced images are also written there, under images.names[i] or "<i as 5 digits>.png".
     ensemble: as evaluate() -- 2, 4 or 8 views of the padded input, the merged result scored.
+    loe: True -- each output is also scored with LOE (loe(), sampler loe_sample) against its input as supplied: to_uint8 of the
+    fp32 input before the reflect pad and before ** gamma.  UnpairedResult.loe is the mean, per_image["loe"] the values; NIQE is
+    untouched.  False: nothing of it runs, UnpairedResult.loe is NaN.  The reference has no LOE.
     The model's attributes and the train / eval mode of every submodule are restored afterwards.
-    Not reproduced: BRISQUE; and the score is the quantized output's, not that of a lossy file decoded again (.jpg names)."""
+    Not reproduced: BRISQUE (its place as the second unpaired number is taken by the opt-in LOE); and the score is the quantized
+    output's, not that of a lossy file decoded again (.jpg names)."""
     prm = _niqe_params(params)
 
     def load(i, img, device):
@@ -846,10 +923,16 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
         if x.shape[1] < NIQE_BLOCK or x.shape[2] < NIQE_BLOCK:
             raise ValueError(f"evaluate_unpaired: image {i} is {x.shape[1]} x {x.shape[2]}; NIQE needs at least "
                              f"{NIQE_BLOCK} x {NIQE_BLOCK} pixels")
-        return x, None
-    return _evaluate("evaluate_unpaired", "images", model, images, load, dict(gated2=True), lambda q, _: (niqe(q, prm),),
-                     ("niqe",), functools.partial(UnpairedResult, ensemble=int(ensemble)), alpha, gamma, batch_size, process_group,
-                     save_dir, ensemble=ensemble)
+        return x, (to_uint8(x) if loe else None)
+
+    def score(q, lows):
+        if not loe:
+            return (niqe(q, prm),)
+        low = torch.stack(lows) if len(lows) > 1 else lows[0].unsqueeze(0)
+        return niqe(q, prm), _loe_launch(low, q, loe_sample)[1]      # loe(): the keyword shadows its name in here
+    return _evaluate("evaluate_unpaired", "images", model, images, load, dict(gated2=True), score,
+                     ("niqe", "loe") if loe else ("niqe",), functools.partial(UnpairedResult, ensemble=int(ensemble)), alpha,
+                     gamma, batch_size, process_group, save_dir, ensemble=ensemble)
 
 
 class FolderImages:

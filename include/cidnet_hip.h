@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 17
+#define CIDNET_ABI_VERSION 18
 
 int cidnet_abi_version(void);
 
@@ -616,6 +616,30 @@ int cidnet_metric_niqe_fit(const double* moments, const double* tables, int bloc
 long cidnet_metric_niqe_ws_floats(int B, int h, int w);
 int cidnet_metric_niqe_features(const uint8_t* rgb, const double* window, const double* tables, double* feat, float* ws,
                                 long ws_floats, int B, int h, int w, void* stream);
+
+/* ---- LOE, the lightness order error (Wang et al. 2013, the paper of the NPE set): the second no-reference number of the
+ * unpaired sets beside NIQE.  The reference has no LOE; the contract is this text.  low, out: planar uint8 (B,3,h,w) on the
+ * device, the image as supplied and its enhancement.  Lightness L(p) = max(R, G, B) of a pixel, 0..255.  The sampling grid
+ * is the caller's `step` (hvi-cidnet_amd/metrics.py: loe_grid): rows = h / step, cols = w / step (integer division), sample
+ * (i, j) is pixel (i step, j step), m = rows cols; only those pixels are read.  With U(a, b) = 1 if a >= b else 0, L from low
+ * and Le from out:
+ *   num[b] = sum over all m x m ordered sample pairs (x, y), y = x included, of U(L(x), L(y)) xor U(Le(x), Le(y))   (int64)
+ *   loe[b] = (double) num[b] / (double) m, the classic form, 0 .. m.  num is always exact; for m <= 2^26 it is below 2^53, so
+ *   the division is the only rounding (beyond that, up to the 2^30 limit below, the conversion of num rounds as well).
+ * Formed from the 256 x 256 joint histogram of (L, Le) (csrc/loe.hip: the identity and the two launches), so the cost is
+ * O(m + 65536) per image.  ws: cidnet_metric_loe_ws_bytes(B) bytes, 16-byte aligned: B x 65536 32-bit bins, zeroed inside
+ * the call.  low / out / num / loe / ws NULL, a misaligned ws, B, h, w or step < 1, or step > min(h, w) is CIDNET_ERR_ARG; a
+ * short workspace CIDNET_ERR_WS; m > 2^30 or B > 65535 CIDNET_ERR_SHAPE.  Integer atomics only (no floating-point atomics, no
+ * hand-off between blocks inside a launch): bit-identical from call to call, and an image's values do not depend on the rest
+ * of the batch.
+ * plan: host only, launches nothing; the function the launcher itself calls.  Writes out[0..5] = rows, cols, blocks per image
+ *   of the histogram launch, samples per block (blocks x samples >= m), counter bits of a block's LDS sub-histogram (16: a
+ *   block takes fewer than 2^16 samples, so a counter cannot carry into the one packed beside it), dynamic LDS bytes per block.
+ *   out NULL or n < 6 is CIDNET_ERR_ARG and nothing is written; never writes past out[5]; the size errors are those above. */
+long cidnet_metric_loe_ws_bytes(int B);
+int cidnet_metric_loe_plan(int h, int w, int step, int* out, int n);
+int cidnet_metric_loe_u8(const uint8_t* low, const uint8_t* out, int B, int h, int w, int step, long long* num, double* loe,
+                         void* ws, long ws_bytes, void* stream);
 
 /* ---- Training batches from a resident uint8 set (data/data.py:6-12 transform1 + train.py:54-56 of the reference): random
  * crop, horizontal / vertical flip, ToTensor and the gamma power of one batch, low image and ground truth, in one launch.
