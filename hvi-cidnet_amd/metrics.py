@@ -28,7 +28,13 @@ and LOE, the lightness order error of the enhanced image against the low input (
     v = M.loe(low_u8, q, sample=50)                 # (B,) float64 on the device: num / m (normalized=True: num / m^2)
     res = M.evaluate_unpaired(model, images, prm, loe=True)     # res.loe, res.per_image["loe"]
 
-The kernels are csrc/metrics.hip, csrc/resize.hip, csrc/niqe.hip and csrc/loe.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
+and the file round trip of the .jpg sets (eval.py saves such an output as a JPEG and the reference scores the decoded file):
+
+    plan = M.jpeg_quant_plan(75)                    # host: the tables Pillow writes, the divisors, the exact-division constants
+    r = M.jpeg_roundtrip_u8(q, quality=75)          # uint8 (B,3,h,w) -> what PIL's save(.., 'JPEG') + open() returns, byte for byte
+    res = M.evaluate_unpaired(model, images, prm, file_roundtrip=True)      # .jpg / .jpeg names scored as their decoded files
+
+The kernels are csrc/metrics.hip, csrc/resize.hip, csrc/niqe.hip, csrc/loe.hip and csrc/jpeg.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
 Differences from the reference scripts, none of which changes a per-image value:
   * measure.py counts a low image without a ground truth in the divisor of its averages (it skips the image after
     `n += 1`); here such an image is skipped and reported (FolderPairs.skipped, EvalResult.skipped) and not counted;
@@ -40,14 +46,13 @@ Differences from the reference scripts, none of which changes a per-image value:
   * LPIPS is not computed (it needs AlexNet weights and the lpips package's heads);
   * NIQE: the half-size image sums its 8 taps in fp64 and rounds once per pass where the reference sums them in fp32 (two
     fp32 ulps apart at most), and the block moments are summed in fp64 where the reference's are fp32 means; an image with
-    fewer than two NaN-free blocks scores NaN (the reference raises from inside the SVD); BRISQUE is not computed, and the
-    score is that of the quantized output itself: for a .jpg input eval.py's output file is a JPEG, and the reference scores
-    what that file decodes to (save_dir= writes the same file; its lossy round trip is not in the score).
+    fewer than two NaN-free blocks scores NaN (the reference raises from inside the SVD); BRISQUE is not computed; and by
+    default the score is that of the quantized output itself, while for a .jpg input eval.py's output file is a JPEG and the
+    reference scores what that file decodes to: evaluate_unpaired(file_roundtrip=True) scores exactly that.
 """
 from __future__ import annotations
 
 import contextlib
-import functools
 import math
 import os
 import warnings
@@ -885,6 +890,96 @@ def loe(low_u8: torch.Tensor, out_u8: torch.Tensor, sample=50, normalized: bool 
     return num.to(torch.float64) / torch.full((), float(m * m), dtype=torch.float64, device=num.device)
 
 
+# ---- JPEG file round trip (eval.py saves a .jpg input's output as a JPEG; measure_niqe_bris.py scores the decoded file) --------
+# Annex K.1 / K.2 of the JPEG standard, in natural (row-major) order: the tables libjpeg's jpeg_set_quality scales
+_JPEG_STD_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+                  14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+                  49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_JPEG_STD_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+                    47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+JPEG_EXTENSIONS = (".jpg", ".jpeg")                                # lower-cased: the names PIL saves as JPEG
+_jpeg_plans = {}                                                   # quality -> JpegQuantPlan
+_jpeg_plans_dev = {}                                               # (device index, quality) -> the int32 (2,2,64) table there
+
+
+@dataclass(frozen=True)
+class JpegQuantPlan:
+    """What quantising at one quality needs (jpeg_quant_plan); the arrays are read-only.  A coefficient v of libjpeg's scaled
+    forward DCT becomes sign(v) ((|v| + (d >> 1)) // d) t with d = 8 t; the kernel forms the quotient as the high 32 bits of
+    (|v| + (d >> 1)) * magic, magic = ceil(2^32 / d): exact for every numerator below 2^16 (n d < 2^32)."""
+    quality: int
+    luma: np.ndarray                                               # int32 (8,8), 1..255
+    chroma: np.ndarray                                             # int32 (8,8)
+    divisors: np.ndarray                                           # int32 (2,8,8): 8 t, luma then chroma
+    magic: np.ndarray                                              # int64 (2,8,8): ceil(2^32 / (8 t)), at most 2^29
+    shift: int = 32
+
+    def device_table(self) -> np.ndarray:
+        """int32 (2,2,64), what cidnet_metric_jpeg_roundtrip_u8 reads: per component the table, then the constants"""
+        t = np.stack([self.luma, self.chroma]).reshape(2, 64)
+        return np.ascontiguousarray(np.stack([t, self.magic.reshape(2, 64)], axis=1).astype(np.int32))
+
+
+def _jpeg_magic(divisor: int) -> int:
+    """ceil(2^32 / divisor): floor(n / divisor) is the high word of n * it whenever n * divisor < 2^32"""
+    return -((-1 << 32) // int(divisor))
+
+
+def jpeg_quant_plan(quality: int = 75) -> JpegQuantPlan:
+    """The baseline quantisation tables Pillow writes at `quality` (1..100) with its defaults -- Annex K scaled by s = 5000 //
+    q below 50, else 200 - 2 q: t = clamp((std s + 50) // 100, 1, 255) -- with the divisors 8 t and the exact-division
+    constants of the kernel.  Pure host code; cached per quality."""
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise ValueError(f"jpeg_quant_plan: quality must be an integer in 1..100 (got {quality!r})")
+    q = int(quality)
+    if q not in _jpeg_plans:
+        s = 5000 // q if q < 50 else 200 - 2 * q
+        tabs = [np.clip((np.array(std, dtype=np.int64) * s + 50) // 100, 1, 255).reshape(8, 8) for std in
+                (_JPEG_STD_LUMA, _JPEG_STD_CHROMA)]
+        div = np.stack(tabs) * 8
+        arrays = (tabs[0].astype(np.int32), tabs[1].astype(np.int32), div.astype(np.int32),
+                  np.array([_jpeg_magic(d) for d in div.reshape(-1)], dtype=np.int64).reshape(2, 8, 8))
+        for a in arrays:
+            a.setflags(write=False)
+        _jpeg_plans[q] = JpegQuantPlan(q, *arrays)
+    return _jpeg_plans[q]
+
+
+def _jpeg_table_on(device, quality):
+    """uploaded once per process, device and quality"""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), int(quality))
+    if key not in _jpeg_plans_dev:
+        _jpeg_plans_dev[key] = torch.from_numpy(jpeg_quant_plan(quality).device_table()).to(device)
+    return _jpeg_plans_dev[key]
+
+
+def jpeg_roundtrip_u8(q: torch.Tensor, quality: int = 75) -> torch.Tensor:
+    """uint8 (B,3,h,w) (or (3,h,w)) on the device -> uint8 of the same form: per image what PIL's Image.open() returns for the
+    file Image.save(f, 'JPEG', quality=quality) writes of it (4:2:0, baseline tables: Pillow's defaults, as eval.py saves a
+    .jpg), byte for byte and without the file: the lossy stages of libjpeg in its own fixed-point arithmetic (csrc/jpeg.hip,
+    DESIGN.md 6.10).  A non-contiguous view is read as its values.  w < 5, h < 1 or a quality outside 1..100: ValueError."""
+    if not isinstance(q, torch.Tensor):
+        raise RuntimeError("jpeg_roundtrip_u8: expected a tensor")
+    _on_device(q)
+    if q.dtype != torch.uint8:
+        raise RuntimeError(f"jpeg_roundtrip_u8 takes uint8 images (got {q.dtype}); see to_uint8")
+    plan = jpeg_quant_plan(quality)
+    squeeze = q.dim() == 3
+    x = _batched(q, "jpeg_roundtrip_u8")
+    B, _, h, w = x.shape
+    if h < 1 or w < 5 or B < 1:
+        raise ValueError(f"jpeg_roundtrip_u8: images of at least 1 x 5 pixels are needed (got {B} of {h} x {w}): libjpeg's "
+                         "decoder reads padded columns of narrower ones")
+    L = lib()
+    n = L.raw("cidnet_metric_jpeg_ws_bytes")(B, h, w)
+    ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        L.call("cidnet_metric_jpeg_roundtrip_u8", ops._p(x), ops._p(out), ops._p(ws), n, ops._p(_jpeg_table_on(x.device, plan.quality)),
+               B, h, w, ops._stream())
+    return out[0] if squeeze else out
+
+
 @dataclass
 class UnpairedResult:
     """Mean NIQE -- and mean LOE, where evaluate_unpaired(loe=True) asked for it, else NaN -- over the evaluated images (running
@@ -898,7 +993,8 @@ class UnpairedResult:
 
 
 def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batch_size: int = 1, process_group=None,
-                      save_dir=None, ensemble: int = 1, loe: bool = False, loe_sample=50):
+                      save_dir=None, ensemble: int = 1, loe: bool = False, loe_sample=50, file_roundtrip: bool = False,
+                      jpeg_quality: int = 75):
     """eval.py --unpaired + measure_niqe_bris.py on the device.  `images`: a sequence of (3,h,w) float images in [0, 1] (or
     uint8 HWC images, converted as ToTensor() does; folder_images() yields these), each at least 96 x 96.  Each is reflect-
     padded to a multiple of 8, run through model(pow(x, gamma)) in eval mode under no_grad with trans.gated2 = True and
@@ -913,25 +1009,48 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
     loe: True -- each output is also scored with LOE (loe(), sampler loe_sample) against its input as supplied: to_uint8 of the
     fp32 input before the reflect pad and before ** gamma.  UnpairedResult.loe is the mean, per_image["loe"] the values; NIQE is
     untouched.  False: nothing of it runs, UnpairedResult.loe is NaN.  The reference has no LOE.
+    file_roundtrip: True -- an image whose name (images.names[i]) ends, lower-cased, in .jpg or .jpeg is scored as
+    measure_niqe_bris.py scores it: eval.py saves its output under the input's name, so PIL writes a JPEG of quality
+    jpeg_quality (75, PIL's default) and the score is that of the decoded file.  The quantized, cropped output goes through
+    jpeg_roundtrip_u8 (the file's lossy stages on the device, byte-equal to PIL's save + open) and the result is what NIQE --
+    and LOE, when asked for -- sees.  Other names and unnamed images are untouched, each image of a batch by its own name;
+    per_image["file_roundtrip"] holds one bool per image.  save_dir still receives the un-round-tripped output: its .jpg,
+    decoded again, is exactly what was scored.  False: nothing of it runs and the result is what it was without the keyword.
     The model's attributes and the train / eval mode of every submodule are restored afterwards.
-    Not reproduced: BRISQUE (its place as the second unpaired number is taken by the opt-in LOE); and the score is the quantized
-    output's, not that of a lossy file decoded again (.jpg names)."""
+    Not reproduced: BRISQUE (its place as the second unpaired number is taken by the opt-in LOE).  Without file_roundtrip=True
+    the score is the quantized output's, not that of a lossy file decoded again (.jpg names: DICM, NPE, VV)."""
     prm = _niqe_params(params)
+    names = getattr(images, "names", None)
+    if file_roundtrip:
+        jpeg_quant_plan(jpeg_quality)                            # a bad quality raises before anything runs
+    lossy = [bool(file_roundtrip) and names is not None and os.path.splitext(str(names[i]))[1].lower() in JPEG_EXTENSIONS
+             for i in range(len(images))]
 
     def load(i, img, device):
         x = _image_f32(img, device)
         if x.shape[1] < NIQE_BLOCK or x.shape[2] < NIQE_BLOCK:
             raise ValueError(f"evaluate_unpaired: image {i} is {x.shape[1]} x {x.shape[2]}; NIQE needs at least "
                              f"{NIQE_BLOCK} x {NIQE_BLOCK} pixels")
-        return x, (to_uint8(x) if loe else None)
+        return x, ((to_uint8(x) if loe else None), lossy[i])
 
-    def score(q, lows):
+    def score(q, aux):
+        flagged = [k for k, a in enumerate(aux) if a[1]]
+        if len(flagged) == len(aux):
+            q = jpeg_roundtrip_u8(q, jpeg_quality)
+        elif flagged:                                            # a batch of mixed names: each image its own treatment
+            q = q.clone()
+            q[flagged] = jpeg_roundtrip_u8(q[flagged], jpeg_quality)
         if not loe:
             return (niqe(q, prm),)
-        low = torch.stack(lows) if len(lows) > 1 else lows[0].unsqueeze(0)
+        low = torch.stack([a[0] for a in aux]) if len(aux) > 1 else aux[0][0].unsqueeze(0)
         return niqe(q, prm), _loe_launch(low, q, loe_sample)[1]      # loe(): the keyword shadows its name in here
+
+    def result(per_image, **kw):
+        if file_roundtrip:
+            per_image["file_roundtrip"] = list(lossy)
+        return UnpairedResult(per_image=per_image, ensemble=int(ensemble), **kw)
     return _evaluate("evaluate_unpaired", "images", model, images, load, dict(gated2=True), score,
-                     ("niqe", "loe") if loe else ("niqe",), functools.partial(UnpairedResult, ensemble=int(ensemble)), alpha,
+                     ("niqe", "loe") if loe else ("niqe",), result, alpha,
                      gamma, batch_size, process_group, save_dir, ensemble=ensemble)
 
 

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 18
+#define CIDNET_ABI_VERSION 19
 
 int cidnet_abi_version(void);
 
@@ -640,6 +640,33 @@ long cidnet_metric_loe_ws_bytes(int B);
 int cidnet_metric_loe_plan(int h, int w, int step, int* out, int n);
 int cidnet_metric_loe_u8(const uint8_t* low, const uint8_t* out, int B, int h, int w, int step, long long* num, double* loe,
                          void* ws, long ws_bytes, void* stream);
+
+/* ---- JPEG file round trip (eval.py saves a .jpg input's output under the input's name: Pillow writes a quality-75 4:2:0
+ * baseline JPEG, and measure_niqe_bris.py scores what that file decodes to).  src (B,3,h,w) -> dst (B,3,h,w), planar uint8 on
+ * the device: dst is what Image.open() returns for the file Image.save(f, 'JPEG', quality=q) writes of src, byte for byte,
+ * without the file -- the entropy coder is lossless, so only the lossy stages run, all in libjpeg's 32-bit fixed point
+ * (csrc/jpeg.hip): RGB -> YCbCr, h2v2 downsampling of the edge-replicated chroma (the DOWNSAMPLED rows are
+ * replicated to whole blocks), jfdctint's forward DCT, c = sign(v) ((|v| + 4 t) / (8 t)) t per coefficient, jidctint's inverse
+ * DCT, "fancy" h2v2 upsampling of the (ceil(h/2), ceil(w/2)) chroma planes, YCbCr -> RGB.
+ * qtab: 256 int32 on the device (hvi-cidnet_amd/metrics.py: jpeg_quant_plan): for luma, then chroma, the 64 table entries t
+ *   (1..255, natural row-major order) and then the 64 constants ceil(2^32 / (8 t)): the quotient is the high word of
+ *   (|v| + 4 t) * constant, exact for every numerator below 2^16.  The table lives on the device and cannot be checked here
+ *   without a copy; no address depends on it, so a broken table gives wrong bytes and nothing else.
+ * ws: cidnet_metric_jpeg_ws_bytes(B, h, w) bytes (host only; 0 for sizes the launcher refuses), 16-byte aligned: per image the
+ *   decoded luma plane and the two chroma planes over whole MCUs, 384 bytes per 16 x 16 MCU.
+ * src / dst / ws / qtab NULL, a misaligned ws or qtab, B or h < 1, or w < 5 is CIDNET_ERR_ARG (libjpeg's decoder reads padded
+ * columns of a chroma plane narrower than three samples: not reproduced); a short workspace CIDNET_ERR_WS; h or w > 65500
+ * (no such file exists), more than 2^22 MCUs, or B > 65535 CIDNET_ERR_SHAPE.  Integer arithmetic only, no atomics, no
+ * reductions: a byte depends on its own MCU and its chroma neighbours alone, bit-identical from call to call and independent of
+ * the rest of the batch.  src and dst must not overlap.
+ * plan: host only, launches nothing; the function the launcher itself calls.  Writes out[0..8] = MCU columns, MCU rows,
+ *   whether the right MCUs are partial (w % 16 != 0), whether the bottom ones are (h % 16 != 0), rows and columns of a chroma
+ *   plane, workgroups per MCU row of the first launch (8 MCUs each), its workgroups per image, workspace bytes per image.
+ *   out NULL or n < 9 is CIDNET_ERR_ARG and nothing is written; never writes past out[8]; the size errors are those above. */
+long cidnet_metric_jpeg_ws_bytes(int B, int h, int w);
+int cidnet_metric_jpeg_plan(int h, int w, int* out, int n);
+int cidnet_metric_jpeg_roundtrip_u8(const uint8_t* src, uint8_t* dst, void* ws, long ws_bytes, const int* qtab, int B, int h,
+                                    int w, void* stream);
 
 /* ---- Training batches from a resident uint8 set (data/data.py:6-12 transform1 + train.py:54-56 of the reference): random
  * crop, horizontal / vertical flip, ToTensor and the gamma power of one batch, low image and ground truth, in one launch.
