@@ -46,11 +46,28 @@ class FlatAdam:
     device (`state`: applied, skipped), and every step runs the guard first (ops.grad_guard: fp64 norm of the averaged
     gradient, clip_grad_norm_'s coefficient, skip when the gradient holds a NaN or an Inf and skip_nonfinite is set), then an
     Adam update that reads the guard's record; nothing of it reaches the host.  With all three off this is the plain update
-    with a host step count.  kernel=False restates the same decisions in torch (CPU tests; it synchronises)."""
+    with a host step count.  kernel=False restates the same decisions in torch (CPU tests; it synchronises).
+
+    ema_decay: keep `ema`, an exponential moving average of the whole buffer (a copy of flat_p at construction): after every
+    Adam launch, on the same stream, ema += w * (p - ema) over the live part with w = fp32(1 - decay) (ops.ema_update; three
+    fp32 roundings).  On the device-state path the launch reads the guard's record, so a skipped step leaves the average
+    where it is.
+    accum_steps > 1: the optimizer also owns `acc`, the buffer the passes of an accumulated update are summed in, and
+    accumulate(), the one operation on it (dst = src or dst += src, ops.grad_accumulate); the trainer decides when."""
 
     def __init__(self, flat_p, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, kernel: bool = True,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, device_state: bool = False):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, device_state: bool = False,
+                 accum_steps: int = 1, ema_decay: Optional[float] = None):
         self.p = flat_p
+        self.accum_steps = int(accum_steps)
+        if self.accum_steps < 1:
+            raise ValueError("accum_steps must be at least 1")
+        if self.accum_steps > 1:
+            self.acc = torch.zeros_like(flat_p)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        if self.ema_decay is not None:
+            self.ema_w = ema_weight(self.ema_decay)
+            self.ema = flat_p.detach().clone()
         self.m = torch.zeros_like(flat_p)
         self.v = torch.zeros_like(flat_p)
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
@@ -92,9 +109,41 @@ class FlatAdam:
         if self.kernel:
             from . import ops
             ops.adam_step(p, g, m, v, self.lr, b1, b2, self.eps, self.wd, self.t, grad_scale)
+        else:
+            # plain-torch restatement of the same update (used by the CPU/gloo tests of the harness only)
+            self._torch_update(p, g, m, v, grad_scale, self.t)
+        self._ema_update(n_live, None)
+
+    def _ema_update(self, n_live, record, applied=True):
+        """the average follows the update that was just launched: same stream, behind the Adam kernel"""
+        if self.ema_decay is None:
             return
-        # plain-torch restatement of the same update (used by the CPU/gloo tests of the harness only)
-        self._torch_update(p, g, m, v, grad_scale, self.t)
+        e, p = self.ema[:n_live], self.p[:n_live]
+        if self.kernel:
+            from . import ops
+            ops.ema_update(e, p, self.ema_w, record)
+        elif applied:
+            e.add_((p - e).mul_(self.ema_w))           # three roundings, as the kernel: difference, product, sum
+
+    def accumulate(self, dst, src, first: bool):
+        """dst = src (first) or dst += src, one rounding per element, on the current stream"""
+        if self.kernel:
+            from . import ops
+            ops.grad_accumulate(dst, src, first)
+        elif first:
+            dst.copy_(src)
+        else:
+            dst.add_(src)
+
+    def swap_ema(self):
+        """exchange p and ema in place (whole buffers: the dead tail is the same on both sides)"""
+        if self.kernel:
+            from . import ops
+            ops.swap(self.p, self.ema)
+        else:
+            t = self.p.clone()
+            self.p.copy_(self.ema)
+            self.ema.copy_(t)
 
     def _torch_update(self, p, g, m, v, gscale, t):
         b1, b2 = self.betas
@@ -116,6 +165,7 @@ class FlatAdam:
             ops.grad_guard(g, grad_scale, self.max_grad_norm if self._clips() else None, self.skip_nonfinite, b1, b2, loss,
                            self.state, self.record, log_row)
             ops.adam_step_dev(p, g, m, v, self.lr, b1, b2, self.eps, self.wd, self.record)
+            self._ema_update(p.numel(), self.record)
             return
         # plain-torch restatement of the guard's decisions (CPU/gloo tests; reads the sum on the host)
         ss = float(g.double().pow(2).sum().item())
@@ -133,6 +183,16 @@ class FlatAdam:
                                         applied if apply else -(applied + 1)], dtype=torch.float64))
         if apply:
             self._torch_update(p, g, m, v, grad_scale * coef, applied)
+        self._ema_update(p.numel(), None, applied=apply)
+
+
+def ema_weight(decay) -> float:
+    """w = fp32(1 - decay), the difference formed in double: the factor of ema += w * (p - ema)"""
+    import ctypes
+    d = float(decay)
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"ema_decay must be in [0, 1) (got {decay!r})")
+    return ctypes.c_float(1.0 - d).value
 
 
 class StepLog:
@@ -213,11 +273,31 @@ class DataParallelTrainer:
                  process_group=None, use_hip_kernels: bool = True, wgrad_stream: bool = True, use_graph: bool = False,
                  max_steps_in_flight: int = 3, max_queued_bytes: Optional[int] = None,
                  prepared_weights: Optional[bool] = None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False, step_log: Optional[StepLog] = None):
+                 skip_nonfinite: bool = False, step_log: Optional[StepLog] = None, accum_steps: int = 1,
+                 ema_decay: Optional[float] = None):
         """max_grad_norm / skip_nonfinite / step_log: the guarded step (FlatAdam's device-state path).  The guard runs after
         the all-reduce, where every rank holds the same gradient, so every rank takes the same decision without talking;
-        step_log (a StepLog) receives one row per step."""
+        step_log (a StepLog) receives one row per step.
+
+        accum_steps = K > 1: step() is called once per micro-batch and every K-th call applies one update from the sum of the
+        K gradients, added in fp32 in pass order, with grad_scale 1 / (world * K); the first K - 1 calls launch no
+        collective, the K-th one all-reduce per bucket.  A micro-batch's gradient is the gradient of its OWN mean loss, so a
+        short last batch weighs as much as a full one.  The step log gets one row per update (the loss: the fp32 sum of the
+        passes' losses in pass order, times fp32(1 / K)); pending_passes, flush().
+        ema_decay: an exponential moving average of the weights, updated on the device behind every Adam launch and left
+        alone by a step the guard skips (FlatAdam); ema_state_dict(), ema_weights().
+        With the defaults neither adds a launch, a value or a state_dict key."""
         self.model = model
+        self.accum_steps = int(accum_steps)
+        if self.accum_steps < 1:
+            raise ValueError("accum_steps must be at least 1")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        if self.ema_decay is not None:
+            ema_weight(self.ema_decay)               # range check now, not at the first step
+        self._passes = 0                             # passes of the open accumulation group
+        self._comm_pass = True                       # this pass's buckets are all-reduced as they complete ...
+        self._fold_pass = False                      # ... after they took the earlier passes' sum (step() sets both)
+        self._in_ema = False                         # inside ema_weights(): flat_p holds the average
         self.step_log = step_log
         self.prepared_weights = (os.environ.get("CIDNET_PREPARED_WEIGHTS", "1") == "1") if prepared_weights is None else bool(prepared_weights)
         # Back-pressure.  Nothing in a training step synchronises host and device, and the host enqueues a step in ~13 ms
@@ -357,7 +437,12 @@ class DataParallelTrainer:
             self._prep = ops.PreparedWeights() if self.prepared_weights else None
         for p in live:
             p.register_post_accumulate_grad_hook(self._on_grad)
-        self.opt = FlatAdam(self.flat_p, kernel=self.use_hip, **self._opt_args)
+        # after the broadcast: the average starts as a copy of the weights every rank holds
+        self.opt = FlatAdam(self.flat_p, kernel=self.use_hip, accum_steps=self.accum_steps, ema_decay=self.ema_decay,
+                            **self._opt_args)
+        if self.accum_steps > 1:
+            self._loss_acc = torch.zeros(1, device=dev, dtype=torch.float32)     # the open group's loss sum
+            self._loss_mean = torch.zeros(1, device=dev, dtype=torch.float32)    # what the guard logs for the update
         if self.step_log is not None:
             self.step_log.bind(dev)
         self._ready = True
@@ -430,17 +515,23 @@ class DataParallelTrainer:
         p.grad = None                               # the arena is the single home of gradients
         bi = self._bucket_of[id(p)]
         self._pending[bi] -= 1
-        if self._pending[bi] == 0 and (self.world > 1 or self._force_comm) and not self._capturing:
+        if self._pending[bi] == 0 and (self.world > 1 or self._force_comm) and not self._capturing and self._comm_pass:
             self._launch_bucket(bi)
 
     def _launch_bucket(self, bi):
         """All-reduce one finished bucket without stalling the compute streams.  The bucket's gradients were written
         by kernels on up to three streams (the two branch streams and the weight-gradient stream) and this hook only
         runs in CPU order, so the collective is issued from a dedicated launch stream that first waits for the
-        current tail of every producer stream; RCCL orders its own stream after the launch stream."""
+        current tail of every producer stream; RCCL orders its own stream after the launch stream.
+        In the last pass of an accumulated update the bucket first takes the sum of the earlier passes (flat_acc, complete
+        since the previous pass's accumulate on the main stream, which the launch stream waits for as a producer), on the
+        launch stream and in front of the collective: one all-reduce per bucket per update, still overlapped."""
         start, cnt, _ = self.buckets[bi]
         dev = self.flat_g.device
+        fold = self._fold_pass                    # earlier passes of this update wait in flat_acc
         if dev.type != "cuda":                    # gloo / CPU rehearsal: no streams
+            if fold:
+                self.opt.accumulate(self.flat_g[start:start + cnt], self.opt.acc[start:start + cnt], first=False)
             self._handles.append(dist.all_reduce(self.flat_g[start:start + cnt], op=dist.ReduceOp.SUM, group=self.pg,
                                                  async_op=True))
             return
@@ -455,6 +546,8 @@ class DataParallelTrainer:
             if ps is not None:
                 st.wait_stream(ps)
         with torch.cuda.stream(st):
+            if fold:
+                self.opt.accumulate(self.flat_g[start:start + cnt], self.opt.acc[start:start + cnt], first=False)
             self._handles.append(dist.all_reduce(self.flat_g[start:start + cnt], op=dist.ReduceOp.SUM, group=self.pg,
                                                  async_op=True))
 
@@ -531,6 +624,15 @@ class DataParallelTrainer:
             self._capturing = False
 
     def _graph_step(self, x, gt, raw_input=None):
+        self._graph_replay(x, gt, raw_input)
+        if self.world > 1 or self._force_comm:
+            dist.all_reduce(self.flat_g[:self.n_live], op=dist.ReduceOp.SUM, group=self.pg)
+        self._opt_step(self._gloss)
+        self._weights_changed()          # the captured pass reads prepared operands that the eager passes before it created
+        return self._gloss
+
+    def _graph_replay(self, x, gt, raw_input=None):
+        """forward + loss + backward by replay (captured first where needed); gradients in flat_g, the loss in _gloss"""
         # the graph reads the prepared operands' buffers: recapture once they were dropped, and re-prepare them when a
         # weight was written through torch since the last step (load_state_dict)
         if self._graph is not None and self._prep is not None:
@@ -547,11 +649,6 @@ class DataParallelTrainer:
         if raw_input is not None:
             self._graw.copy_(raw_input)
         self._graph.replay()
-        if self.world > 1 or self._force_comm:
-            dist.all_reduce(self.flat_g[:self.n_live], op=dist.ReduceOp.SUM, group=self.pg)
-        self._opt_step(self._gloss)
-        self._weights_changed()          # the captured pass reads prepared operands that the eager passes before it created
-        return self._gloss
 
     # ---- the step ---------------------------------------------------------------------------------
     def step(self, x, gt, raw_input=None):
@@ -559,6 +656,8 @@ class DataParallelTrainer:
         `wants_input` loss function gets as im1 in place of x (the low image before the gamma power, train_tnsm.py:55,68;
         data.TrainBatches(raw=True) yields it); ValueError with a loss function that takes no input."""
         self._check_raw(raw_input)
+        if self._in_ema:
+            raise RuntimeError("step() inside ema_weights(): the model holds the averaged weights")
         if not self._ready:
             self._setup(x, gt, raw_input)
         if x.is_cuda:
@@ -570,7 +669,9 @@ class DataParallelTrainer:
                 self.max_queued_bytes = torch.cuda.get_device_properties(x.device).total_memory // 3
             while len(self._step_events) > 1 and self._queued_bytes(x.device) > self.max_queued_bytes:
                 self._step_events.pop(0).synchronize()
-        if self.use_graph and x.is_cuda:
+        if self.accum_steps > 1:
+            loss = self._accum_pass(x, gt, raw_input)
+        elif self.use_graph and x.is_cuda:
             loss = self._graph_step(x, gt, raw_input)
         else:
             loss = self._fwd_bwd(x, gt, raw_input)
@@ -586,15 +687,92 @@ class DataParallelTrainer:
             self._step_events.append(ev)
         return loss
 
-    def _opt_step(self, loss):
-        """fused Adam on the arena; guarded: the guard's two launches first, fed the loss tensor the step returns"""
+    def _opt_step(self, loss, flat_g=None, passes: int = 1):
+        """fused Adam on the arena; guarded: the guard's two launches first, fed the loss tensor the step returns.
+        flat_g / passes: the buffer that holds the summed gradient of an accumulated update and how many passes it sums."""
+        flat_g = self.flat_g if flat_g is None else flat_g
+        scale = 1.0 / (self.world * passes)
         if not self.opt.guarded:
-            self.opt.step(self.flat_g, self.n_live, grad_scale=1.0 / self.world)
+            self.opt.step(flat_g, self.n_live, grad_scale=scale)
             return
         row = self.step_log.next_row() if self.step_log is not None else None
         if row is not None and self.opt.kernel:
             row = row.data_ptr()
-        self.opt.step(self.flat_g, self.n_live, grad_scale=1.0 / self.world, loss=loss.detach(), log_row=row)
+        self.opt.step(flat_g, self.n_live, grad_scale=scale, loss=loss.detach(), log_row=row)
+
+    # ---- gradient accumulation --------------------------------------------------------------------------
+    @property
+    def pending_passes(self) -> int:
+        """passes of the open accumulation group (0: no group is open)"""
+        return self._passes
+
+    @property
+    def flat_acc(self):
+        """the sum of the open group's passes (accum_steps > 1, after the first step)"""
+        return self.opt.acc
+
+    @property
+    def ema(self):
+        """the flat average, laid out as flat_p (ema_decay set, after the first step)"""
+        return self.opt.ema
+
+    def _accum_pass(self, x, gt, raw_input):
+        """One micro-batch of an accumulated update.  Passes 1 .. K-1: forward, loss, backward without a collective, then
+        flat_acc (+)= flat_g and the loss sum on the current stream, behind the join with the weight-gradient stream.  Pass
+        K: its buckets take flat_acc on the launch stream before their all-reduce (one rank: flat_g += flat_acc behind the
+        join), then guard and Adam with 1 / (world * K).  The sum handed on is fl(..fl(fl(g1 + g2) + g3).. + gK)."""
+        K, n = self.accum_steps, self.n_live
+        last = self._passes == K - 1
+        comm = self.world > 1 or self._force_comm
+        graph = self.use_graph and x.is_cuda
+        self._comm_pass, self._fold_pass = last, last
+        try:
+            if graph:
+                self._graph_replay(x, gt, raw_input)
+                loss = self._gloss
+            else:
+                loss = self._fwd_bwd(x, gt, raw_input)
+                for h in self._handles:
+                    h.wait()
+                self._join_wgrad_stream()
+        finally:
+            self._comm_pass, self._fold_pass = True, False
+        loss = loss.detach()
+        self.opt.accumulate(self._loss_acc, loss.reshape(1), first=self._passes == 0)
+        if not last:
+            self.opt.accumulate(self.flat_acc[:n], self.flat_g[:n], first=self._passes == 0)
+            self._passes += 1
+            return loss
+        if graph or not comm:                    # eager with ranks: every bucket took its share in _launch_bucket
+            self.opt.accumulate(self.flat_g[:n], self.flat_acc[:n], first=False)
+        if graph and comm:
+            dist.all_reduce(self.flat_g[:n], op=dist.ReduceOp.SUM, group=self.pg)
+        self._apply_update(self.flat_g, K)
+        return loss
+
+    def _apply_update(self, flat_g, passes):
+        """guard + Adam (+ EMA) from the summed gradient of `passes` passes; the logged loss is their fp32 mean"""
+        self._scale_loss(1.0 / passes)
+        self._opt_step(self._loss_mean, flat_g=flat_g, passes=passes)
+        self._passes = 0
+        self._weights_changed()
+
+    def _scale_loss(self, mult):
+        if self.use_hip:
+            from . import ops
+            ops.scale_into(self._loss_mean, self._loss_acc, mult)
+        else:
+            torch.mul(self._loss_acc, mult, out=self._loss_mean)
+
+    def flush(self):
+        """Apply the open group of j < K passes as one update with grad_scale 1 / (world * j); on several ranks flat_acc is
+        all-reduced in one collective.  Nothing happens without an open group.  Every rank must call it alike."""
+        j, n = self._passes, self.n_live
+        if j == 0:
+            return
+        if self.world > 1 or self._force_comm:
+            dist.all_reduce(self.flat_acc[:n], op=dist.ReduceOp.SUM, group=self.pg)
+        self._apply_update(self.flat_acc, j)
 
     # ---- optimizer state ----------------------------------------------------------------------------
     def _live_named(self):
@@ -615,21 +793,45 @@ class DataParallelTrainer:
             if self._pending_state is not None:
                 return self._pending_state
             raise RuntimeError("state_dict: the optimizer exists after the first step (or after load_state_dict)")
+        if self._passes:
+            raise RuntimeError(f"state_dict: an accumulation group is open ({self._passes} of {self.accum_steps} passes); "
+                               "finish it or flush() first")
+        if self._in_ema:
+            raise RuntimeError("state_dict inside ema_weights(): weights and average are exchanged")
         o = self.opt
-        return {"exp_avg": {n: o.m[off:off + c].view(shp).cpu().clone() for n, off, c, shp in self._live_named()},
-                "exp_avg_sq": {n: o.v[off:off + c].view(shp).cpu().clone() for n, off, c, shp in self._live_named()},
-                "steps_applied": o.steps_applied(), "steps_skipped": o.steps_skipped(), "lr": float(o.lr),
-                "betas": tuple(float(b) for b in o.betas), "eps": float(o.eps), "weight_decay": float(o.wd)}
+        out = {"exp_avg": {n: o.m[off:off + c].view(shp).cpu().clone() for n, off, c, shp in self._live_named()},
+               "exp_avg_sq": {n: o.v[off:off + c].view(shp).cpu().clone() for n, off, c, shp in self._live_named()},
+               "steps_applied": o.steps_applied(), "steps_skipped": o.steps_skipped(), "lr": float(o.lr),
+               "betas": tuple(float(b) for b in o.betas), "eps": float(o.eps), "weight_decay": float(o.wd)}
+        if self.ema_decay is not None:
+            out["ema"] = {n: o.ema[off:off + c].view(shp).cpu().clone() for n, off, c, shp in self._live_named()}
+            out["ema_decay"] = self.ema_decay
+        return out
 
     def load_state_dict(self, state):
         """Strict: the names must be exactly the live parameters, the shapes theirs.  Before the first step the state is
         checked against the model's names and shapes and applied once the arena exists; which parameters are live is only
-        known then, so a missing or dead name raises there.  lr, betas, eps and weight decay are taken over at once."""
+        known then, so a missing or dead name raises there.  lr, betas, eps and weight decay are taken over at once.
+        The average: with ema_decay set the state must carry "ema" (same names as exp_avg) and "ema_decay"; without it the
+        state must carry neither.  The trainer keeps its own ema_decay."""
         for k in ("exp_avg", "exp_avg_sq", "steps_applied", "steps_skipped", "lr", "betas", "eps", "weight_decay"):
             if k not in state:
                 raise KeyError(f"load_state_dict: missing entry '{k}'")
+        if self.ema_decay is not None:
+            for k in ("ema", "ema_decay"):
+                if k not in state:
+                    raise KeyError(f"load_state_dict: this trainer keeps an EMA (ema_decay={self.ema_decay}), the state has no '{k}'")
+        elif "ema" in state or "ema_decay" in state:
+            raise KeyError("load_state_dict: the state carries an EMA, this trainer was built without ema_decay")
+        if self._passes:
+            raise RuntimeError("load_state_dict: an accumulation group is open; finish it or flush() first")
+        if self._in_ema:
+            raise RuntimeError("load_state_dict inside ema_weights()")
+        moments = ("exp_avg", "exp_avg_sq") + (("ema",) if self.ema_decay is not None else ())
         shapes = {n: tuple(p.shape) for n, p in self.model.named_parameters()}
-        for k in ("exp_avg", "exp_avg_sq"):
+        if "ema" in moments and set(state["ema"]) != set(state["exp_avg"]):
+            raise KeyError("load_state_dict: ema and exp_avg name different parameters")
+        for k in moments:
             for n, t in state[k].items():
                 if n not in shapes:
                     raise KeyError(f"load_state_dict: {k} has an entry for '{n}', which is no parameter of the model")
@@ -660,6 +862,55 @@ class DataParallelTrainer:
             o.m[off:off + c].copy_(state["exp_avg"][n].reshape(-1))
             o.v[off:off + c].copy_(state["exp_avg_sq"][n].reshape(-1))
         o.set_counts(state["steps_applied"], state["steps_skipped"])
+        if self.ema_decay is not None:
+            for n, off, c, shp in live:
+                o.ema[off:off + c].copy_(state["ema"][n].reshape(-1))
+            o.ema[self.n_live:].copy_(self.flat_p[self.n_live:])      # the dead tail stays the copy of the weights
+
+    # ---- the averaged weights -------------------------------------------------------------------------
+    def _need_ema(self, what):
+        if self.ema_decay is None:
+            raise RuntimeError(f"{what}: this trainer was built without ema_decay")
+        if not self._ready:
+            raise RuntimeError(f"{what}: the average exists after the first step")
+
+    def ema_state_dict(self):
+        """The averaged model: the keys of model.state_dict(), CPU tensors; the trainer's parameters come from `ema` by the
+        arena's slices (the ones that get no gradient as the copy of their weights), buffers and anything else are copied
+        from the model.  Loads into a fresh model with strict=True.  Synchronises."""
+        self._need_ema("ema_state_dict")
+        if self._in_ema:
+            raise RuntimeError("ema_state_dict inside ema_weights(): weights and average are exchanged")
+        names = {n: p for n, p in self.model.named_parameters()}
+        out = {}
+        for k, v in self.model.state_dict().items():
+            sl = self._slices.get(id(names[k])) if k in names else None
+            if sl is None:
+                out[k] = v.detach().cpu().clone()
+            else:
+                out[k] = self.opt.ema[sl[0]:sl[0] + sl[1]].view(v.shape).cpu().clone()
+        return out
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside, the model computes with the averaged weights: `ema` and flat_p are exchanged in place (ops.swap: no
+        third copy of the weights) and the prepared operands rebuilt; on exit, also after an exception, the same again, which
+        restores both bit for bit.  Raises inside an open accumulation group; a training step inside raises."""
+        self._need_ema("ema_weights")
+        if self._passes:
+            raise RuntimeError(f"ema_weights: an accumulation group is open ({self._passes} of {self.accum_steps} passes); "
+                               "finish it or flush() first")
+        if self._in_ema:
+            raise RuntimeError("ema_weights: already inside")
+        self.opt.swap_ema()
+        self._weights_changed()
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self.opt.swap_ema()
+            self._weights_changed()
+            self._in_ema = False
 
     def _weights_changed(self):
         if self._prep is not None and self.flat_p.is_cuda:

@@ -42,10 +42,14 @@ _SCHEDULE_KEYS = ("nEpochs", "lr", "warmup_epochs", "start_warmup", "start_epoch
 
 
 def run_epoch(trainer, batches, epoch, step_log):
-    """The steps of one epoch and ONE read of the step log -> its rows, (steps, 4) fp64 (dp.StepLog's columns)"""
+    """The steps of one epoch and ONE read of the step log -> its rows, (updates, 4) fp64 (dp.StepLog's columns).  With
+    accum_steps = K > 1 a batch is one pass and a row one update; a group the epoch's last batch leaves open is applied
+    from the passes it has (trainer.flush), so 61 batches with K = 4 are 16 updates, the last from one pass."""
     step_log.reset()
     for batch in batches.epoch(epoch):                           # (x, gt) or (x, gt, raw): the third is the step's raw_input
         trainer.step(*batch)
+    if trainer.pending_passes > 0:
+        trainer.flush()
     return step_log.read()
 
 
@@ -72,7 +76,7 @@ def _model_device(model):
 
 def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, start_epoch=0, snapshots=10, loss_fn=None,
         max_grad_norm=None, skip_nonfinite=True, val_pairs=None, val_args=None, out_dir=None, resume=None,
-        process_group=None, on_epoch=None, trainer_args=None):
+        process_group=None, on_epoch=None, trainer_args=None, accum_steps=1, ema_decay=None, val_weights="model"):
     """Train `model` for the epochs start_epoch + 1 ... start_epoch + nEpochs and return one record per epoch.
 
     batches: anything with __len__ (steps per epoch) and epoch(e) yielding (x, gt) or (x, gt, raw): data.TrainBatches.
@@ -91,7 +95,20 @@ def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, star
     resume = path of an epoch_*.train.pt: the exact one.  The trainer's state and the epoch counter come from the file, the
     model's weights from the epoch_*.pth beside it, the schedule continues where it was (its arguments must be the file's);
     since data.epoch_plan is a function of (seed, epoch) and every reduction of a step has a fixed order, the run continues
-    bit-identically.  trainer_args: further DataParallelTrainer arguments."""
+    bit-identically.  trainer_args: further DataParallelTrainer arguments.
+    accum_steps = K: every batch is one pass of an update summed over K of them (DataParallelTrainer); `steps`, `skipped` and
+    the loss of the record then count updates, ceil(len(batches) / K) per epoch, the last one from the batches that are left.
+    ema_decay: the trainer keeps an exponential moving average of the weights; a snapshot also writes epoch_{epoch}.ema.pth
+    (trainer.ema_state_dict(), the same checkpoint format) and `resume=` restores the average with the rest.
+    val_weights: "model" validates the trained weights (psnr / ssim), "ema" the averaged ones (psnr_ema / ssim_ema,
+    evaluated inside trainer.ema_weights()), "both" both; "ema" and "both" need ema_decay."""
+    if val_weights not in ("model", "ema", "both"):
+        raise ValueError(f"fit: val_weights must be 'model', 'ema' or 'both' (got {val_weights!r})")
+    if val_weights != "model" and ema_decay is None:
+        raise ValueError(f"fit: val_weights={val_weights!r} needs ema_decay")
+    accum_steps = int(accum_steps)
+    if accum_steps < 1:
+        raise ValueError("fit: accum_steps must be at least 1")
     sched_args = dict(nEpochs=int(nEpochs), lr=float(lr), warmup_epochs=int(warmup_epochs), start_warmup=bool(start_warmup),
                       start_epoch=int(start_epoch))
     sched = WarmupCosineLR(sched_args["lr"], sched_args["nEpochs"], sched_args["warmup_epochs"], sched_args["start_epoch"],
@@ -101,10 +118,10 @@ def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, star
         raise ValueError("fit: snapshots must be positive")
     if len(batches) <= 0:
         raise ValueError("fit: an epoch without steps")
-    log = StepLog(len(batches))
+    log = StepLog(-(-len(batches) // accum_steps))                # one row per update
     trainer = DataParallelTrainer(model, lr=sched.lr_after(0), loss_fn=loss_fn, process_group=process_group,
                                   max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, step_log=log,
-                                  **(trainer_args or {}))
+                                  accum_steps=accum_steps, ema_decay=ema_decay, **(trainer_args or {}))
     first, done = sched_args["start_epoch"] + 1, 0
     if resume is not None:
         saved = torch.load(resume, map_location="cpu", weights_only=False)
@@ -132,9 +149,13 @@ def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, star
         if epoch % snapshots == 0:
             if out_dir is not None and rank == 0:
                 _snapshot(model, trainer, out_dir, epoch, done, sched_args)
-            if val_pairs is not None:
+            if val_pairs is not None and val_weights in ("model", "both"):
                 res = _validate(model, val_pairs, val_args, process_group)
                 rec["psnr"], rec["ssim"] = res.psnr, res.ssim
+            if val_pairs is not None and val_weights in ("ema", "both"):
+                with trainer.ema_weights():
+                    res = _validate(model, val_pairs, val_args, process_group)
+                rec["psnr_ema"], rec["ssim_ema"] = res.psnr, res.ssim
         records.append(rec)
         if on_epoch is not None:
             on_epoch(rec)
@@ -155,3 +176,5 @@ def _snapshot(model, trainer, out_dir, epoch, done, sched_args):
     torch.save({k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, os.path.join(out_dir, name))
     torch.save({"trainer": trainer.state_dict(), "epoch": int(epoch), "epochs_done": int(done), "schedule": dict(sched_args),
                 "weights": name}, os.path.join(out_dir, f"epoch_{epoch}.train.pt"))
+    if trainer.ema_decay is not None:
+        torch.save(trainer.ema_state_dict(), os.path.join(out_dir, f"epoch_{epoch}.ema.pth"))

@@ -1205,6 +1205,14 @@ def snapshot(t):
     return y
 
 
+def scale_into(dst, src, mult):
+    """dst = src * fp32(mult) through cidnet_scale, into a buffer the caller keeps (the mean of an accumulated loss sum)"""
+    _check(dst, src)
+    if not (dst.is_contiguous() and src.is_contiguous()) or dst.numel() != src.numel():
+        raise RuntimeError("scale_into: two contiguous fp32 buffers of the same length")
+    lib().call("cidnet_scale", _p(src), None, _f(mult), _p(dst), src.numel(), _stream())
+
+
 class L1LossFn(torch.autograd.Function):
     """mean(|out - gt|): reference L1Loss (loss/losses.py:10-20, loss_utils.py l1_loss, reduction='mean').
     Differentiable in both arguments: train.py:62 does not detach gt_hvi = model.HVIT(gt_rgb), so the HVI-space
@@ -1489,6 +1497,36 @@ def adam_step_dev(p, g, m, v, lr, beta1, beta2, eps, weight_decay, record):
     _check(p, g, m, v, record)
     lib().call("cidnet_adam_step_dev", _p(p), _p(g), _p(m), _p(v), p.numel(), _f(lr), _f(beta1), _f(beta2), _f(eps),
                _f(weight_decay), _p(record), _stream())
+
+
+def _flat_pair(what, a, b):
+    _check(a, b)
+    if not (a.is_contiguous() and b.is_contiguous()) or a.numel() != b.numel() or a.numel() == 0:
+        raise RuntimeError(f"{what}: two contiguous fp32 buffers of the same, non-zero length")
+
+
+def grad_accumulate(dst, src, first):
+    """cidnet_grad_accumulate on the current stream: dst = src (first) or dst += src, each sum rounded once.  Slices of a
+    flat buffer at any 4-byte-aligned offset and of any length; also the 1-element loss sum."""
+    _flat_pair("grad_accumulate", dst, src)
+    lib().call("cidnet_grad_accumulate", _p(dst), _p(src), dst.numel(), int(bool(first)), _stream())
+
+
+def ema_update(ema, p, w, record=None):
+    """cidnet_ema_update on the current stream: ema += w * (p - ema) in three roundings; with a guard record whose apply is
+    0 the launch leaves ema alone.  w: dp.ema_weight(decay)."""
+    _flat_pair("ema_update", ema, p)
+    if record is not None:
+        _check(record)
+        if record.numel() < GUARD_RECORD_FLOATS:
+            raise RuntimeError("ema_update: record must be the guard's 4-float record")
+    lib().call("cidnet_ema_update", _p(ema), _p(p), ema.numel(), _f(w), _p(record), _stream())
+
+
+def swap(a, b):
+    """cidnet_swap on the current stream: exchange two non-overlapping buffers in place"""
+    _flat_pair("swap", a, b)
+    lib().call("cidnet_swap", _p(a), _p(b), a.numel(), _stream())
 
 
 # --------------------------------------------------------------------------------------------

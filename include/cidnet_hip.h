@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 19
+#define CIDNET_ABI_VERSION 20
 
 int cidnet_abi_version(void);
 
@@ -479,6 +479,21 @@ int cidnet_grad_guard(const float* g, long n, float grad_scale, float max_norm, 
  * apply is 0, p, m and v are not touched. */
 int cidnet_adam_step_dev(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                          float eps, float weight_decay, const float* record, void* stream);
+/* Elementwise passes over slices of the trainer's flat fp32 buffers (csrc/accum.hip).  Common contract: any n >= 1, bases
+ * aligned to 4 bytes only (a scalar head up to the first 16-byte boundary of the written buffer, 16-byte accesses in the
+ * grid-stride body, a scalar tail); nothing outside [0, n) is read or written; no atomics; every fp32 operation is rounded
+ * on its own (no fma), so repeated calls and a numpy fp32 restatement are bit-identical.
+ *   grad_accumulate: dst[i] = first ? src[i] : dst[i] + src[i].  The gradient sum of an accumulated update (pass order is
+ *                    the caller's launch order) and, with n = 1, the sum of its scalar losses.
+ *   ema_update:      ema[i] = ema[i] + w * (p[i] - ema[i]) (three roundings), w = fp32(1 - decay) formed by the caller in
+ *                    double.  record: a cidnet_grad_guard record or NULL; with a record whose apply ([0]) is 0 every block
+ *                    returns before it touches ema (a skipped step does not pull the average towards unchanged weights).
+ *                    A launch of its own behind cidnet_adam_step / cidnet_adam_step_dev on the same stream.
+ *   swap:            exchanges a[0..n) and b[0..n) in place; the two ranges must not overlap (CIDNET_ERR_ARG).  Twice is the
+ *                    identity, bit for bit. */
+int cidnet_grad_accumulate(float* dst, const float* src, long n, int first, void* stream);
+int cidnet_ema_update(float* ema, const float* p, long n, float w, const float* record, void* stream);
+int cidnet_swap(float* a, float* b, long n, void* stream);
 
 /* ---- K13: SpatialAttention of the MSSA variant (net/CIDNet_MSSA.py:10-25) ------------------------
  * out = x * sigmoid(conv7x7([mean_c x, max_c x])), w: (1,2,7,7).  stats (B,2,H,W), amax (B,H,W int32)

@@ -5,12 +5,15 @@ per measurement:
                  timing, host clock around work that ends in a device synchronise
   epoch          one epoch of run_epoch (the step log read once at the end) against the same epoch with loss.item() after
                  every step (the reference's way, train.py:75), alternated three times, over a synthetic resident set
+  accum_ema      --accum K and / or --ema DECAY: ms per pass of the guarded step with accum_steps=K / ema_decay=DECAY against
+                 the guarded step without them, alternated three times (nothing else is measured in such a run)
   kernels        --share PATH: time per launch of the guard's kernels from the kernel_stats.csv of a run under
                  rocprofv3 --kernel-trace --stats (a run of its own: --trace-run launches only a few guarded steps)
 
 Every line is printed and appended to --out (default profiles/fit_<precision>.jsonl; --share: profiles/fit_kernels.jsonl).
 
     python tools/bench_fit.py [--precision f32|bf16] [--steps 20] [--pairs 64] [--out FILE]
+    python tools/bench_fit.py [--precision f32|bf16] [--steps 20] --accum 4 --ema 0.999
     rocprofv3 --kernel-trace --stats -f csv -d OUT -o run -- python tools/bench_fit.py --trace-run
     python tools/bench_fit.py --share OUT/.../run_kernel_stats.csv
 """
@@ -64,6 +67,8 @@ def main():
     ap.add_argument("--pairs", type=int, default=64, help="size of the synthetic resident set (an epoch has pairs / 8 steps)")
     ap.add_argument("--trace-run", action="store_true", help="a few guarded steps only (for a rocprofv3 run)")
     ap.add_argument("--share", default=None, help="kernel_stats.csv of a rocprofv3 run of this tool with --trace-run")
+    ap.add_argument("--accum", type=int, default=1, help="K: time the guarded step with accum_steps=K against the plain one")
+    ap.add_argument("--ema", type=float, default=None, help="DECAY: time the guarded step with ema_decay=DECAY against the plain one")
     ap.add_argument("--out", default=None, help="file the JSON lines are appended to")
     a = ap.parse_args()
     global _OUT
@@ -86,6 +91,32 @@ def main():
         kw = dict(max_grad_norm=1.0, skip_nonfinite=True, step_log=P.StepLog(capacity)) if guard else {}
         return DataParallelTrainer(P.CIDNet().to(dev), lr=1e-4, **kw)
 
+    if a.accum > 1 or a.ema is not None:
+        # the guarded step without and with accumulation / the average, alternated; ms per PASS (one B = 8 batch), so the two
+        # compare directly: with --accum K a timing runs steps - steps % K passes, i.e. whole updates
+        torch.manual_seed(0)
+        plain = trainer(True)
+        torch.manual_seed(0)
+        feat = DataParallelTrainer(P.CIDNet().to(dev), lr=1e-4, max_grad_norm=1.0, skip_nonfinite=True,
+                                   step_log=P.StepLog(64), accum_steps=a.accum, ema_decay=a.ema)
+        passes = max(a.accum, a.steps - a.steps % a.accum)
+        pair = {"plain": plain, "feature": feat}
+        for tr in pair.values():
+            for _ in range(2 * a.accum if a.accum > 1 else 5):
+                tr.step(x0, gt0)
+        torch.cuda.synchronize()
+        for rep in range(3):
+            for name, tr in pair.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(passes):
+                    tr.step(x0, gt0)
+                torch.cuda.synchronize()
+                t = time.perf_counter() - t0
+                emit({"what": "accum_ema", "precision": a.precision, "mode": name, "accum": a.accum if name == "feature" else 1,
+                      "ema": a.ema if name == "feature" else None, "rep": rep, "passes": passes,
+                      "ms_per_pass": t / passes * 1e3})
+        return
     trainers = {"guard_off": trainer(False), "guard_on": trainer(True)}
     for tr in trainers.values():
         for _ in range(5):
