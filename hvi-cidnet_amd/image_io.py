@@ -30,6 +30,16 @@ the reference has no such mode.  Not combined with tile=.
 The kernels are csrc/imageio.hip (C ABI: cidnet_image_ingest / cidnet_image_egress and their _tiles forms) and
 csrc/ensemble.hip (cidnet_ensemble_views / cidnet_ensemble_merge), semantics in include/cidnet_hip.h.
 
+PNG files from the device, opt-in (png="pillow", the default everywhere, is the path above, untouched, with no new launch):
+    p = png_plan(h, w, segment_bytes=32768)        # host: rows per segment, segments, workspace bytes, slot capacity (a bound)
+    streams, sizes = png_zlib_u8(q)                # uint8 (B,h,w,3) -> the zlib stream of each image's IDAT chunk, on the device
+    data = png_file(h, w, stream_bytes)            # host: signature, IHDR, IDAT, IEND and the CRC-32s around one stream
+    files = png_encode_u8(q)                       # the two together: a list of bytes (synchronises)
+    report = enhance_folder(model, in_dir, out_dir, png="device")
+The stream is "adaptive row filters, one dynamic-Huffman deflate block per segment of rows, literals only" (DESIGN.md 6.12,
+csrc/png.hip): the files decode to exactly the pixels Pillow's would and are smaller than Pillow's on photographs; flat
+synthetic content compresses badly (no LZ77: one bit per byte at the least).
+
 enhance_folder is a pipeline; who owns what, and when:
   * decode workers (min(threads, 16)) read one file each through PIL's .convert('RGB') and write its bytes into a pinned
     per-image staging buffer that the main thread handed them; a buffer still too small is grown by the main thread;
@@ -47,9 +57,12 @@ from __future__ import annotations
 import collections
 import concurrent.futures as cf
 import functools
+import ctypes
 import os
+import struct
 import threading
 import time
+import zlib
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -455,6 +468,106 @@ def enhance_u8(model, images_u8: torch.Tensor, gamma: float = 1.0, gated: bool =
         return _run(model, t, table, views)
 
 
+# ---- PNG files: the IDAT stream from the device, the framing on the host ------------------------------------------------------
+PNG_FILTERS = ("none", "sub", "up", "avg", "paeth", "adaptive")  # the position is the C ABI's filter code
+_PNG_MODES = ("pillow", "device")
+
+
+@dataclass(frozen=True)
+class PngPlan:
+    """cidnet_png_plan for one image size: rows per segment (the contract's R, not clipped to h), segments, whether the last
+    one is short, whether a single row exceeds segment_bytes, workspace bytes per image, and capacity: a proven bound on one
+    stream's size, the size of an output slot"""
+    rows: int
+    segments: int
+    last_short: bool
+    row_exceeds: bool
+    ws_bytes: int
+    capacity: int
+
+
+def _check_png(png):
+    if png not in _PNG_MODES:
+        raise ValueError(f"png must be 'pillow' or 'device' (got {png!r})")
+    return png
+
+
+def _png_args(filter, segment_bytes):
+    if filter not in PNG_FILTERS:
+        raise ValueError(f"png: filter must be one of {PNG_FILTERS} (got {filter!r})")
+    if isinstance(segment_bytes, bool) or not isinstance(segment_bytes, (int, np.integer)) or not 1 <= int(segment_bytes) < 2 ** 31:
+        raise ValueError(f"png: segment_bytes must be an integer in 1 .. 2^31 - 1 (got {segment_bytes!r})")
+    return PNG_FILTERS.index(filter), int(segment_bytes)
+
+
+@functools.lru_cache(maxsize=256)
+def _png_plan(h, w, segment_bytes):
+    out = (ctypes.c_long * 6)()
+    rc = lib().raw("cidnet_png_plan")(h, w, segment_bytes, out, 6)
+    if rc != 0:
+        raise ValueError(f"png_plan: a {h} x {w} image in segments of {segment_bytes} bytes is refused: "
+                         + ("sizes must be positive" if rc == -1 else "a segment (or one row) of more than 2^22 bytes"))
+    return PngPlan(int(out[0]), int(out[1]), bool(out[2]), bool(out[3]), int(out[4]), int(out[5]))
+
+
+def png_plan(h, w, segment_bytes: int = 32768) -> PngPlan:
+    """What png_zlib_u8 will do with (h, w) images: the library's own plan (host code, nothing is launched).  ValueError for a
+    non-positive size and for a segment -- or a single row -- of more than 2^22 bytes."""
+    return _png_plan(_whole(h), _whole(w), _png_args("adaptive", segment_bytes)[1])
+
+
+def _png_zlib(t, code, segment_bytes):
+    """checked (B,h,w,3) -> (buf, streams, sizes): one flat uint8 buffer holding sizes (int64 (B,), padded to 16 bytes) and
+    then the B slots, and the two views into it -- one buffer so that one copy brings both to the host"""
+    B, h, w, _ = t.shape
+    plan = _png_plan(h, w, segment_bytes)
+    head = (8 * B + 15) // 16 * 16
+    buf = torch.empty(head + B * plan.capacity, dtype=torch.uint8, device=t.device)
+    sizes, streams = buf[:8 * B].view(torch.int64), buf[head:].view(B, plan.capacity)
+    ws = torch.empty(B * plan.ws_bytes, dtype=torch.uint8, device=t.device)
+    with torch.cuda.device(t.device):
+        lib().call("cidnet_png_encode_u8", ops._p(t), t.stride(0) if B > 1 else 3 * h * w, ops._p(streams), plan.capacity,
+                   ops._p(sizes), ops._p(ws), ws.numel(), B, h, w, code, segment_bytes, ops._stream())
+    return buf, streams, sizes
+
+
+def png_zlib_u8(q: torch.Tensor, filter: str = "adaptive", segment_bytes: int = 32768):
+    """uint8 (B,h,w,3) (or (h,w,3)) on the device, as egress writes it -> (streams uint8 (B, capacity), sizes int64 (B,)), both
+    on the device, no synchronisation: streams[b, :sizes[b]] is the complete zlib stream of image b's IDAT chunk (png_file
+    frames it), the rest of the slot is zero; capacity = png_plan(h, w, segment_bytes).capacity.  filter: "adaptive" (per row
+    the type with the smallest sum of |signed filtered byte|, ties to the lowest) or one of "none", "sub", "up", "avg", "paeth"
+    for every row.  segment_bytes: a deflate block takes max(1, segment_bytes // (1 + 3 w)) rows.  The bytes are those of
+    tests/png_ref.py, identical from call to call and independent of the rest of the batch."""
+    code, segment_bytes = _png_args(filter, segment_bytes)
+    if isinstance(q, torch.Tensor) and not q.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    t = _images_u8(q, "png_zlib_u8")
+    _, streams, sizes = _png_zlib(t, code, segment_bytes)
+    return streams, sizes
+
+
+def _png_chunk(tag, data):
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data))
+
+
+def png_file(h, w, stream_bytes) -> bytes:
+    """The PNG file around one zlib stream (host): signature, IHDR (8-bit, colour type 2, no interlace), one IDAT, IEND"""
+    h, w = _whole(h), _whole(w)
+    if not (0 < h < 2 ** 31 and 0 < w < 2 ** 31):
+        raise ValueError(f"png_file: the image must be positive (got {(h, w)})")
+    return (b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
+            + _png_chunk(b"IDAT", bytes(stream_bytes)) + _png_chunk(b"IEND", b""))
+
+
+def png_encode_u8(q: torch.Tensor, filter: str = "adaptive", segment_bytes: int = 32768) -> list:
+    """uint8 (B,h,w,3) (or (h,w,3)) on the device -> the B PNG files as bytes: png_zlib_u8, one download, png_file.  The
+    convenience form: it synchronises."""
+    streams, sizes = png_zlib_u8(q, filter, segment_bytes)
+    h, w = (q.shape[-3], q.shape[-2])
+    host, n = streams.cpu().numpy(), sizes.cpu().tolist()
+    return [png_file(h, w, host[b, :n[b]].tobytes()) for b in range(len(n))]
+
+
 # ---- the batching plan (pure host code) -------------------------------------------------------------------------------
 def shard(n, rank=0, world=1):
     """input positions of rank's images: i % world == rank, in input order"""
@@ -478,9 +591,15 @@ class _Writer:
     non-blocking copy into a pinned buffer on the download stream and one encode task per image, which waits for that copy's
     event in its worker and saves through PIL.  At most `depth` batches are in flight: put() first retires the oldest one
     (waits for its futures; the time goes to `waited`) when they are.  on_done() of a batch runs when it is retired.  The
-    first exception of a worker surfaces from retire() / put() / close() with the file's name."""
+    first exception of a worker surfaces from retire() / put() / close() with the file's name.
+    png="device": a batch with a path ending in .png (any case) is also encoded by png_zlib_u8 on the current stream right
+    behind q; the download stream copies the sizes and the capacity-strided slots in ONE further non-blocking copy into a pinned
+    buffer of their own, and the worker of such a path frames stream[:size] with png_file and writes it.  Paths of other
+    extensions keep PIL; q itself is downloaded only when one of them is in the batch."""
 
-    def __init__(self, device, threads=8, depth=2):
+    def __init__(self, device, threads=8, depth=2, png="pillow"):
+        self.png = _check_png(png)
+        self.host_png = [None] * max(1, int(depth))              # pinned: sizes and slots of a batch's PNG streams
         self.device, self.depth = device, max(1, int(depth))
         self.pool = cf.ThreadPoolExecutor(max_workers=max(1, min(int(threads), 16)), thread_name_prefix="cidnet-encode")
         self.down = torch.cuda.Stream(device)
@@ -498,6 +617,21 @@ class _Writer:
             event.synchronize()
             n = 3 * h * w
             Image.fromarray(host[k * n:(k + 1) * n].view(h, w, 3).numpy()).save(path)
+        except Exception as e:
+            raise RuntimeError(f"image_io: {os.path.basename(path)}: could not be written: {e}") from e
+
+    def _save_png(self, event, host, head, capacity, k, h, w, path):
+        if self.stop.is_set():
+            return
+        try:
+            event.synchronize()
+            size = int(host[8 * k:8 * k + 8].view(torch.int64)[0])
+            if not 0 < size <= capacity:
+                raise RuntimeError(f"the encoder reported {size} bytes for a slot of {capacity}")
+            o = head + k * capacity
+            data = png_file(h, w, host[o:o + size].numpy().tobytes())
+            with open(path, "wb") as f:
+                f.write(data)
         except Exception as e:
             raise RuntimeError(f"image_io: {os.path.basename(path)}: could not be written: {e}") from e
 
@@ -523,19 +657,33 @@ class _Writer:
         slot = self.count % self.depth
         self.count += 1
         n = q.numel()
-        if self.host[slot] is None or self.host[slot].numel() < n:
+        on_device = [self.png == "device" and str(p).lower().endswith(".png") for p in paths]
+        buf = None
+        if any(on_device):                                       # the whole batch: its other images' slots are not used
+            buf, streams, _ = _png_zlib(_images_u8(q, "image_io"), PNG_FILTERS.index("adaptive"), 32768)
+            head, capacity = buf.numel() - streams.numel(), streams.shape[1]
+            if self.host_png[slot] is None or self.host_png[slot].numel() < buf.numel():
+                self.host_png[slot] = torch.empty(buf.numel(), dtype=torch.uint8, pin_memory=True)
+            host_png = self.host_png[slot]
+        if not all(on_device) and (self.host[slot] is None or self.host[slot].numel() < n):
             self.host[slot] = torch.empty(n, dtype=torch.uint8, pin_memory=True)
         host = self.host[slot]
         ready = torch.cuda.Event()
-        ready.record()                                           # q is complete here on the current stream
+        ready.record()                                           # q (and its streams) are complete here on the current stream
         self.down.wait_event(ready)
         with torch.cuda.stream(self.down):
-            host[:n].view(B, h, w, 3).copy_(q, non_blocking=True)
+            if not all(on_device):
+                host[:n].view(B, h, w, 3).copy_(q, non_blocking=True)
+            if buf is not None:
+                host_png[:buf.numel()].copy_(buf, non_blocking=True)
         q.record_stream(self.down)
+        if buf is not None:
+            buf.record_stream(self.down)
         done = torch.cuda.Event()
         done.record(self.down)
-        futures = [self.pool.submit(self._save, done, host, k, h, w, p) for k, p in enumerate(paths)]
-        self.inflight.append((futures, on_done, q))
+        futures = [self.pool.submit(self._save_png, done, host_png, head, capacity, k, h, w, p) if dev
+                   else self.pool.submit(self._save, done, host, k, h, w, p) for k, (p, dev) in enumerate(zip(paths, on_device))]
+        self.inflight.append((futures, on_done, (q, buf)))
 
     def close(self):
         try:
@@ -557,13 +705,15 @@ class EnhanceReport:
     """What one rank's enhance_folder did: names / sizes (h, w) of its images in input order, batches (the input positions of
     each launch), seconds: {"wall": the call, "wait_for_slot": of it, the main thread waiting for a batch in flight to
     finish so that its buffers come free}, tiles: with tile=, the number of tiles of each image (empty otherwise), ensemble:
-    the number of views each image was averaged over (1: none were built)"""
+    the number of views each image was averaged over (1: none were built), png: who encoded the .png files ("pillow" or
+    "device")"""
     names: list = field(default_factory=list)
     sizes: list = field(default_factory=list)
     batches: list = field(default_factory=list)
     seconds: dict = field(default_factory=dict)
     tiles: list = field(default_factory=list)
     ensemble: int = 1
+    png: str = "pillow"
 
 
 class _Stage:
@@ -592,7 +742,7 @@ def _decode(stop, path, name, stage):
 @torch.no_grad()
 def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
                    alpha: float = 1.0, batch_size: int = 1, threads: int = 8, depth: int = 2, process_group=None, tile=None,
-                   overlap: int = 32, tile_batch: int = 8, ensemble: int = 1) -> EnhanceReport:
+                   overlap: int = 32, tile_batch: int = 8, ensemble: int = 1, png: str = "pillow") -> EnhanceReport:
     """eval.py / demo.py for a folder: every image file of in_dir (metrics.folder_images: its files and order) is enhanced as
     enhance_u8 does and saved to out_dir/<same file name> by PIL in the format its extension names (the reference's
     output_img.save(output_folder + name[0])); out_dir is created.  Decoding, the device and encoding overlap (module
@@ -604,8 +754,13 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
     tile = T or (Th, Tw): every image is tiled on its own as enhance_u8(tile=, overlap=, tile_batch=) does, one image per
     launch group (batch_size is ignored); the pipeline around it is the same.  report.tiles holds each image's tile count.
     ensemble = 2, 4 or 8: every batch is self-ensembled as enhance_u8(ensemble=) does (the model sees batches of batch_size *
-    views); ValueError for another value or together with tile=, before a worker starts."""
+    views); ValueError for another value or together with tile=, before a worker starts.
+    png: "pillow" -- every file is encoded by PIL.  "device" -- an output whose name ends in .png (any case) is encoded on the
+    device (png_zlib_u8 behind egress: adaptive filters, Huffman coding, no LZ77) and only framed and written by its worker:
+    the same pixels in another, valid PNG file, independent of batch_size, threads and depth; other extensions keep PIL.
+    report.png says which.  ValueError for another value, before a worker starts."""
     views = _check_ensemble(ensemble, tile)
+    png = _check_png(png)
     t_start = time.perf_counter()
     device = metrics._model_device(model)
     if device.type != "cuda":
@@ -622,7 +777,7 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
         batch_size, tile_batch = 1, _tile_batch(tile_batch)
     workers = max(1, min(int(threads), 16))
     mine = list(shard(len(files), rank, world))
-    report = EnhanceReport(names=[files.names[i] for i in mine], ensemble=int(ensemble))
+    report = EnhanceReport(names=[files.names[i] for i in mine], ensemble=int(ensemble), png=png)
     os.makedirs(out_dir, exist_ok=True)
     if not mine:
         report.seconds = {"wall": time.perf_counter() - t_start, "wait_for_slot": 0.0}
@@ -630,7 +785,7 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
 
     stop = threading.Event()
     decoders = cf.ThreadPoolExecutor(max_workers=workers, thread_name_prefix="cidnet-decode")
-    writer = _Writer(device, workers, depth)
+    writer = _Writer(device, workers, depth, png=png)
     # depth batches in flight + the batch being formed + the image _plan looks ahead
     free = [_Stage() for _ in range((depth + 1) * batch_size + 1)]
     pending = collections.deque()                                # decodes submitted, not yet consumed: (position, stage, future)

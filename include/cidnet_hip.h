@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 20
+#define CIDNET_ABI_VERSION 21
 
 int cidnet_abi_version(void);
 
@@ -730,6 +730,44 @@ int cidnet_augment_crop_flip_raw(const uint8_t* arena, const long* plan, const f
 int cidnet_image_ingest(const uint8_t* src, long src_bs, const float* table, float* x, int B, int h, int w, int Hp, int Wp,
                         void* stream);
 int cidnet_image_egress(const float* x, uint8_t* dst, long dst_bs, int B, int Hp, int Wp, int h, int w, void* stream);
+
+/* ---- PNG files written from the device (csrc/png.hip, csrc/png_codes.h; tests/png_ref.py restates the
+ * stream in numpy and is the contract, byte for byte).  src: B interleaved (h,w,3) uint8 images, image b at src + b *
+ * src_stride (>= 3 h w, any byte alignment) -> slot b at dst + b * dst_stride: the complete zlib stream of the image's one IDAT
+ * chunk, sizes[b] bytes of it (int64), the rest of the slot's first `capacity` bytes zero.  The host adds the signature, IHDR,
+ * the chunk lengths and CRC-32s.
+ *   Rows: one type byte + 3 w filtered bytes, PNG's filters with bpp = 3 (left / up / up-left 0 outside the image, Avg =
+ *   floor((left + up) / 2), Paeth ties left, up, up-left).  filter 0..4 forces None / Sub / Up / Avg / Paeth on every row; 5
+ *   (adaptive) takes per row the type with the smallest sum of min(v, 256 - v) over its filtered bytes, ties to the lowest type;
+ *   every candidate is computed from the RAW previous row, so rows are independent.
+ *   Segments: R = max(1, segment_bytes / (1 + 3 w)) whole rows each, the last possibly fewer; one deflate block (BTYPE 2) per
+ *   segment, BFINAL on the last, concatenated at bit granularity.  Literals only: HLIT = 0 (257 codes: the byte counts and the
+ *   end of block with count 1), HDIST = 1 (two distance codes of length 1), HCLEN = 15, the 259 lengths sent as plain symbols
+ *   0..15.  Code lengths: cidnet_png_code_lengths' procedure, limit 15, and limit 7 for the code-length code (one used symbol
+ *   there: symbol 0, or 1 if 0 is the used one, also gets length 1).  Codes canonical (RFC 1951 3.2.2).
+ *   Framing: 0x78 0x01, the blocks, zero bits to the next byte, Adler-32 of the filtered bytes, big-endian.
+ * ws: B * plan[4] bytes, 16-byte aligned (filtered bytes and one record per segment).  dst 4-byte aligned, dst_stride a multiple
+ * of 4 and >= the plan's capacity; sizes 8-byte aligned.  Nothing outside the first `capacity` bytes of the B slots, sizes[0..B)
+ * and the workspace is written.  Integer arithmetic only; the only atomics are integer ORs and adds whose result does not depend
+ * on their order: the bytes are identical from call to call and independent of the rest of the batch.  Three launches.
+ * CIDNET_ERR_ARG, before any launch: a NULL pointer, B, h, w or segment_bytes < 1, filter outside 0..5, a slot below the
+ *   capacity, a misaligned dst / dst_stride / ws / sizes, src_stride < 3 h w.  CIDNET_ERR_WS: a short workspace.
+ *   CIDNET_ERR_SHAPE: a segment (or a single row) of more than 2^22 bytes -- a count must fit the sort key of the code-length
+ *   procedure -- or B > 65535.
+ * plan: host only, launches nothing; the function the launcher itself calls.  out[0..5] = rows per segment R, segments, whether
+ *   the last segment is short, whether one row exceeds segment_bytes, workspace bytes per image, the capacity of one slot: a
+ *   proven bound on the stream's size (per segment of n symbols 1887 header bits and 9 n bits where n < 2584, else 11 n; the
+ *   proof is with png_plan in csrc/png.hip), a multiple of 4.  out NULL or n < 6 is CIDNET_ERR_ARG and nothing is written.
+ * code_lengths: host only; the procedure the kernel runs, for the tests.  freq[0..n) counts (each < 2^23), n <= 257 -> lens[0..n):
+ *   used symbols ascending by (count, symbol); two-queue merge, leaves in that order, internal nodes in creation order, the
+ *   smaller head first and the leaf on equal weight; depth = length; while the deepest exceeds maxbits every used count becomes
+ *   (count + 1) >> 1 and the tree is rebuilt; a single used symbol gets length 1; unused symbols 0.  maxbits outside 1..15 is
+ *   CIDNET_ERR_ARG; more used symbols than 2^maxbits is CIDNET_ERR_SHAPE. */
+#define CIDNET_PNG_FILTER_ADAPTIVE 5
+int cidnet_png_plan(int h, int w, int segment_bytes, long* out, int n);
+int cidnet_png_code_lengths(const unsigned* freq, int n, int maxbits, uint8_t* lens);
+int cidnet_png_encode_u8(const uint8_t* src, long src_stride, uint8_t* dst, long dst_stride, long long* sizes, void* ws,
+                         long ws_bytes, int B, int h, int w, int filter, int segment_bytes, void* stream);
 
 /* ---- Tiled enhancement of one large image (hvi-cidnet_amd/image_io.py: tile_plan): the same two conversions seen through
  * overlapping windows of one fixed shape (th, tw), both multiples of 4.  The reference has no such mode; the contract is "the

@@ -13,6 +13,8 @@ global, so a tiled result is not the whole-image result.
 --ensemble N (2, 4 or 8) is geometric self-ensemble: the model runs on N flipped / transposed views of every image and the
 results, mapped back, are averaged (2: the image and its mirror; 4: all flips; 8: the flips and their transposes).  N forwards
 per image; not combined with --tile.
+--png device encodes the .png outputs on the device (row filters and Huffman coding, no match search) and leaves the host only
+the framing: the same pixels in another valid file, smaller than Pillow's on photographs and larger on flat synthetic images.
 """
 import argparse
 import json
@@ -43,6 +45,7 @@ def main(argv=None):
     ap.add_argument("--tile_overlap", type=int, default=32, help="pixels two neighbouring tiles share (at most half a tile)")
     ap.add_argument("--tile_batch", type=int, default=8, help="tiles per model launch")
     ap.add_argument("--ensemble", type=int, choices=(1, 2, 4, 8), default=1, help="views averaged per image (default 1: none)")
+    ap.add_argument("--png", choices=("pillow", "device"), default="pillow", help="who encodes .png outputs (default pillow)")
     a = ap.parse_args(argv)
     if a.ensemble != 1 and a.tile is not None:
         ap.error("--ensemble and --tile cannot be combined")
@@ -65,12 +68,13 @@ def main(argv=None):
         sys.exit(f"no image file (.png .jpg .bmp .JPG .jpeg) in {a.input}")
     rep = P.enhance_folder(model, files, a.output_dir, gamma=a.gamma, gated=a.gated, alpha_s=a.alpha_s, gated2=a.gated2,
                            alpha=a.alpha_i, batch_size=a.batch_size, threads=a.threads, depth=a.depth, tile=a.tile,
-                           overlap=a.tile_overlap, tile_batch=a.tile_batch, ensemble=a.ensemble)
+                           overlap=a.tile_overlap, tile_batch=a.tile_batch, ensemble=a.ensemble, png=a.png)
     wall = rep.seconds["wall"]
     print(json.dumps({"what": "enhance", "input": a.input, "output_dir": a.output_dir, "variant": a.variant, "images": len(rep.names),
                       "batches": len(rep.batches), "seconds": rep.seconds, "images_per_s": len(rep.names) / wall if wall > 0 else None,
                       "missing_keys": missing, "unexpected_keys": unexpected, "names": rep.names,
-                      "sizes": [list(s) for s in rep.sizes], "tile": a.tile, "tiles": rep.tiles, "ensemble": rep.ensemble}))
+                      "sizes": [list(s) for s in rep.sizes], "tile": a.tile, "tiles": rep.tiles, "ensemble": rep.ensemble,
+                      "png": rep.png}))
 
 
 if __name__ == "__main__":
