@@ -18,6 +18,7 @@
 // that every store of launch A is an aligned 8-byte store and needs no mask inside the MCU grid.
 #include "cidnet_hip.h"
 #include "common.h"
+#include "jpeg_front.h"
 
 namespace cidnet {
 namespace {
@@ -53,27 +54,8 @@ int jpeg_plan(int h, int w, JpegPlan* p) {
   return CIDNET_OK;
 }
 
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
-// libjpeg jfdctint.c, one pass over d[0..7]: kFirst -- the row pass (scaled up by 2^2), else the column pass
-template <bool kFirst>
-__device__ __forceinline__ void fdct8(int* d) {
-  const int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
-  const int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
-  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-  constexpr int n = kFirst ? 11 : 15;
-  d[0] = kFirst ? (t10 + t11) * 4 : descale(t10 + t11, 2);
-  d[4] = kFirst ? (t10 - t11) * 4 : descale(t10 - t11, 2);
-  const int e = (t12 + t13) * 4433;
-  d[2] = descale(e + t13 * 6270, n);
-  d[6] = descale(e - t12 * 15137, n);
-  const int z5 = (t4 + t6 + t5 + t7) * 9633;
-  const int z1 = (t4 + t7) * -7373, z2 = (t5 + t6) * -20995, z3 = (t4 + t6) * -16069 + z5, z4 = (t5 + t7) * -3196 + z5;
-  d[7] = descale(t4 * 2446 + z1 + z3, n);
-  d[5] = descale(t5 * 16819 + z2 + z4, n);
-  d[3] = descale(t6 * 25172 + z2 + z3, n);
-  d[1] = descale(t7 * 12299 + z1 + z4, n);
-}
+using jpegfe::descale;
+using jpegfe::fdct8;
 
 // libjpeg jidctint.c, one pass over c[0..7], descaled by kShift (11: the column pass, 18: the row pass)
 template <int kShift>
@@ -104,10 +86,10 @@ __device__ __forceinline__ void quad(const uint8_t* __restrict__ img, long plane
   int sb = 0, sr = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int r = img[o[i]], g = img[plane + o[i]], b = img[2 * plane + o[i]];
-    yv[i] = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
-    sb += (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
-    sr += (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+    int pb, pr;
+    jpegfe::ycc(img[o[i]], img[plane + o[i]], img[2 * plane + o[i]], &yv[i], &pb, &pr);
+    sb += pb;
+    sr += pr;
   }
   *cb = sb;
   *cr = sr;
@@ -160,13 +142,9 @@ __global__ __launch_bounds__(kCodecThreads) void jpeg_codec_kernel(const uint8_t
   const int* qt = qtab + (b >= 4 * kTileMcus ? 128 : 0);         // uniform per wave: waves 0-3 luma, 4 Cb, 5 Cr
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    // c = sign(v) ((|v| + 4 t) / (8 t)) t.  |v| + 4 t < 2^16 (an 8 x 8 DCT of bytes, scaled by 8, stays below 2^15), and for a
-    // numerator below 2^16 and a divisor below 2^11 the high word of n * ceil(2^32 / d) is n / d exactly (n d < 2^32).
+    // c = sign(v) ((|v| + 4 t) / (8 t)) t: jpeg_front.h has the quotient and why it is exact
     const int t = qt[k * 8 + j];
-    const unsigned m = (unsigned)qt[64 + k * 8 + j];
-    const int v = d[k];
-    const int q = (int)__umulhi((unsigned)((v < 0 ? -v : v) + 4 * t), m);
-    d[k] = (v < 0 ? -q : q) * t;
+    d[k] = jpegfe::quantise(d[k], t, (unsigned)qt[64 + k * 8 + j]) * t;
   }
   idct8<11>(d);
 #pragma unroll

@@ -40,6 +40,15 @@ The stream is "adaptive row filters, one dynamic-Huffman deflate block per segme
 csrc/png.hip): the files decode to exactly the pixels Pillow's would and are smaller than Pillow's on photographs; flat
 synthetic content compresses badly (no LZ77: one bit per byte at the least).
 
+JPEG files from the device, opt-in (jpeg="pillow", the default everywhere, is the path above, untouched, with no new launch):
+    p = jpeg_encode_plan(h, w)                     # host: MCU grid, luma blocks, dummy blocks, workspace bytes, slot capacity
+    streams, sizes = jpeg_scan_u8(q, quality=75)   # uint8 (B,h,w,3) -> each image's entropy-coded scan, on the device
+    data = jpeg_file(h, w, 75, scan_bytes)         # host: the 623 bytes of framing, the scan, EOI
+    files = jpeg_encode_u8(q, quality=75)          # the two together: a list of bytes (synchronises)
+    report = enhance_folder(model, in_dir, out_dir, jpeg="device")
+The file is Pillow's own -- Image.fromarray(a).save(f, 'JPEG', quality=q) at its defaults -- byte for byte (DESIGN.md 6.13,
+csrc/jpegenc.hip): baseline, 4:2:0, the Annex K tables, one scan without restart markers.
+
 enhance_folder is a pipeline; who owns what, and when:
   * decode workers (min(threads, 16)) read one file each through PIL's .convert('RGB') and write its bytes into a pinned
     per-image staging buffer that the main thread handed them; a buffer still too small is grown by the main thread;
@@ -568,6 +577,136 @@ def png_encode_u8(q: torch.Tensor, filter: str = "adaptive", segment_bytes: int 
     return [png_file(h, w, host[b, :n[b]].tobytes()) for b in range(len(n))]
 
 
+# ---- JPEG files: the entropy-coded scan from the device, the framing on the host ------------------------------------------------
+_JPEG_MODES = ("pillow", "device")
+_JPEG_NAMES = (".jpg", ".jpeg")                                  # lower-cased: the names PIL saves as JPEG
+# ITU T.81 Annex K.3 - K.6 as a DHT segment carries them: class / id, the number of codes of each length 1..16, the symbols
+_JPEG_DC = bytes(range(12))
+_JPEG_DHT = (
+    (0x00, bytes.fromhex("00010501010101010100000000000000"), _JPEG_DC),
+    (0x10, bytes.fromhex("0002010303020403050504040000017d"), bytes.fromhex(
+        "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a43"
+        "4445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2"
+        "b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")),
+    (0x01, bytes.fromhex("00030101010101010101010000000000"), _JPEG_DC),
+    (0x11, bytes.fromhex("00020102040403040705040400010277"), bytes.fromhex(
+        "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a"
+        "434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9"
+        "aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")))
+_JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
+                28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54,
+                47, 55, 62, 63)
+JPEG_HEADER_BYTES = 623
+
+
+@dataclass(frozen=True)
+class JpegEncodePlan:
+    """cidnet_jpeg_encode_plan for one image size: the MCU grid, the luma blocks libjpeg transforms (ceil(w/8) x ceil(h/8)),
+    the dummy blocks of the edge MCUs beyond them, workspace bytes per image, capacity: a proven bound on one scan's size, the
+    size of an output slot, and groups: the number of partial sums of the bit-offset scan (16 MCUs each)"""
+    mcu_cols: int
+    mcu_rows: int
+    block_cols: int
+    block_rows: int
+    dummies: int
+    ws_bytes: int
+    capacity: int
+    groups: int
+    workgroups: int
+
+
+def _check_jpeg(jpeg):
+    if jpeg not in _JPEG_MODES:
+        raise ValueError(f"jpeg must be 'pillow' or 'device' (got {jpeg!r})")
+    return jpeg
+
+
+@functools.lru_cache(maxsize=256)
+def _jpeg_encode_plan(h, w):
+    out = (ctypes.c_long * 9)()
+    rc = lib().raw("cidnet_jpeg_encode_plan")(h, w, out, 9)
+    if rc != 0:
+        raise ValueError(f"jpeg_encode_plan: a {h} x {w} image is refused: "
+                         + ("sizes must be positive" if rc == -1 else "a side above 65500 or more than 2^22 MCUs"))
+    return JpegEncodePlan(*(int(v) for v in out))
+
+
+def jpeg_encode_plan(h, w) -> JpegEncodePlan:
+    """What jpeg_scan_u8 will do with (h, w) images: the library's own plan (host code, nothing is launched).  ValueError for a
+    non-positive size, a side above 65500 (no such file exists) and more than 2^22 MCUs."""
+    return _jpeg_encode_plan(_whole(h), _whole(w))
+
+
+def _jpeg_scan(t, quality):
+    """checked (B,h,w,3) -> (buf, streams, sizes): one flat uint8 buffer holding sizes (int64 (B,), padded to 16 bytes) and
+    then the B slots, and the two views into it"""
+    B, h, w, _ = t.shape
+    plan = _jpeg_encode_plan(h, w)
+    qplan = metrics.jpeg_quant_plan(quality)
+    head = (8 * B + 15) // 16 * 16
+    buf = torch.empty(head + B * plan.capacity, dtype=torch.uint8, device=t.device)
+    sizes, streams = buf[:8 * B].view(torch.int64), buf[head:].view(B, plan.capacity)
+    ws = torch.empty(B * plan.ws_bytes, dtype=torch.uint8, device=t.device)
+    with torch.cuda.device(t.device):
+        lib().call("cidnet_jpeg_encode_u8", ops._p(t), t.stride(0) if B > 1 else 3 * h * w, ops._p(streams), plan.capacity,
+                   ops._p(sizes), ops._p(ws), ws.numel(), ops._p(metrics._jpeg_table_on(t.device, qplan.quality)), B, h, w,
+                   ops._stream())
+    return buf, streams, sizes
+
+
+def jpeg_scan_u8(q: torch.Tensor, quality: int = 75):
+    """uint8 (B,h,w,3) (or (h,w,3)) on the device, as egress writes it -> (streams uint8 (B, capacity), sizes int64 (B,)), both
+    on the device, no synchronisation: streams[b, :sizes[b]] is the entropy-coded scan of the JPEG file Pillow writes of image
+    b at `quality` with its defaults (jpeg_file frames it), the rest of the slot is zero; capacity =
+    jpeg_encode_plan(h, w).capacity.  The bytes are Pillow's, identical from call to call and independent of the rest of the
+    batch.  ValueError for a quality outside 1..100 and for a size the plan refuses."""
+    metrics.jpeg_quant_plan(quality)
+    if isinstance(q, torch.Tensor) and not q.is_cuda:
+        raise RuntimeError(_NO_CPU)
+    t = _images_u8(q, "jpeg_scan_u8")
+    _, streams, sizes = _jpeg_scan(t, quality)
+    return streams, sizes
+
+
+def _jpeg_segment(marker, payload):
+    return struct.pack(">BBH", 0xFF, marker, len(payload) + 2) + payload
+
+
+@functools.lru_cache(maxsize=64)
+def _jpeg_header(h, w, quality):
+    plan = metrics.jpeg_quant_plan(quality)
+    out = b"\xff\xd8" + _jpeg_segment(0xE0, b"JFIF\0" + struct.pack(">BBBHHBB", 1, 1, 0, 1, 1, 0, 0))
+    for i, t in enumerate((plan.luma, plan.chroma)):
+        flat = t.reshape(64)
+        out += _jpeg_segment(0xDB, bytes([i]) + bytes(int(flat[n]) for n in _JPEG_ZIGZAG))
+    out += _jpeg_segment(0xC0, struct.pack(">BHHB", 8, h, w, 3) + bytes([1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    for tc_th, counts, symbols in _JPEG_DHT:
+        out += _jpeg_segment(0xC4, bytes([tc_th]) + counts + symbols)
+    out += _jpeg_segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+    assert len(out) == JPEG_HEADER_BYTES
+    return out
+
+
+def jpeg_file(h, w, quality, scan_bytes) -> bytes:
+    """The JPEG file around one entropy-coded scan (host): SOI, APP0 (JFIF 1.01, density 1 x 1), the two quantisation tables
+    of jpeg_quant_plan(quality) in zigzag order, SOF0 (8 bits, three components, 2x2 / 1x1 / 1x1), the four Annex K Huffman
+    tables, SOS -- 623 bytes that depend on h, w and quality alone -- then the scan and EOI"""
+    h, w = _whole(h), _whole(w)
+    if not (0 < h <= 65500 and 0 < w <= 65500):
+        raise ValueError(f"jpeg_file: sides must lie in 1..65500 (got {(h, w)})")
+    return _jpeg_header(h, w, metrics.jpeg_quant_plan(quality).quality) + bytes(scan_bytes) + b"\xff\xd9"
+
+
+def jpeg_encode_u8(q: torch.Tensor, quality: int = 75) -> list:
+    """uint8 (B,h,w,3) (or (h,w,3)) on the device -> the B JPEG files as bytes, each what Image.fromarray(a).save(f, 'JPEG',
+    quality=quality) writes: jpeg_scan_u8, one download, jpeg_file.  The convenience form: it synchronises."""
+    streams, sizes = jpeg_scan_u8(q, quality)
+    h, w = (q.shape[-3], q.shape[-2])
+    n = sizes.cpu().tolist()
+    host = streams[:, :max(n)].cpu().numpy()
+    return [jpeg_file(h, w, quality, host[b, :n[b]].tobytes()) for b in range(len(n))]
+
+
 # ---- the batching plan (pure host code) -------------------------------------------------------------------------------
 def shard(n, rank=0, world=1):
     """input positions of rank's images: i % world == rank, in input order"""
@@ -595,10 +734,25 @@ class _Writer:
     png="device": a batch with a path ending in .png (any case) is also encoded by png_zlib_u8 on the current stream right
     behind q; the download stream copies the sizes and the capacity-strided slots in ONE further non-blocking copy into a pinned
     buffer of their own, and the worker of such a path frames stream[:size] with png_file and writes it.  Paths of other
-    extensions keep PIL; q itself is downloaded only when one of them is in the batch."""
+    extensions keep PIL; q itself is downloaded only when one of them is in the batch.
+    jpeg="device": a batch with a path ending in .jpg or .jpeg (any case) is also encoded by jpeg_scan_u8 at quality 75 on the
+    current stream right behind q.  A slot's proven capacity is about three times the raw image and a real scan a small
+    fraction of it, so the download stream copies the sizes and a PREFIX of each slot -- jpeg_prefix * 3 h w bytes, rounded up
+    to 4 KiB, the capacity at most; one non-blocking pinned copy per image, the first carrying the sizes -- and a worker whose
+    image reports size > prefix fetches the remainder itself with a second copy on the download stream and waits for it (the
+    device buffer lives until retire()).  The files do not depend on jpeg_prefix; second_copies counts such images, downloaded
+    the bytes all copies brought to the host.  Both keywords combine in one batch."""
 
-    def __init__(self, device, threads=8, depth=2, png="pillow"):
+    def __init__(self, device, threads=8, depth=2, png="pillow", jpeg="pillow", jpeg_prefix=0.25):
         self.png = _check_png(png)
+        self.jpeg = _check_jpeg(jpeg)
+        if not 0 < float(jpeg_prefix) <= 8:
+            raise ValueError(f"jpeg_prefix must lie in (0, 8] (got {jpeg_prefix!r})")
+        self.jpeg_prefix = float(jpeg_prefix)
+        self.host_jpeg = [None] * max(1, int(depth))             # pinned: sizes and slot prefixes of a batch's JPEG scans
+        self.second_copies = 0
+        self.downloaded = 0
+        self.lock = threading.Lock()
         self.host_png = [None] * max(1, int(depth))              # pinned: sizes and slots of a batch's PNG streams
         self.device, self.depth = device, max(1, int(depth))
         self.pool = cf.ThreadPoolExecutor(max_workers=max(1, min(int(threads), 16)), thread_name_prefix="cidnet-encode")
@@ -635,6 +789,42 @@ class _Writer:
         except Exception as e:
             raise RuntimeError(f"image_io: {os.path.basename(path)}: could not be written: {e}") from e
 
+    def _save_jpeg(self, event, host, buf, head, capacity, prefix, k, h, w, path):
+        if self.stop.is_set():
+            return
+        try:
+            event.synchronize()
+            size = int(host[8 * k:8 * k + 8].view(torch.int64)[0])
+            if not 0 < size <= capacity:
+                raise RuntimeError(f"the encoder reported {size} bytes for a slot of {capacity}")
+            o = head + k * prefix
+            scan = host[o:o + min(size, prefix)].numpy().tobytes()
+            if size > prefix:                                    # the rest of this slot: a copy of its own, waited for here
+                rest = torch.empty(size - prefix, dtype=torch.uint8, pin_memory=True)
+                d = head + k * capacity
+                with torch.cuda.device(self.device), torch.cuda.stream(self.down):
+                    rest.copy_(buf[d + prefix:d + size], non_blocking=True)
+                    fetched = torch.cuda.Event()
+                    fetched.record()
+                fetched.synchronize()
+                scan += rest.numpy().tobytes()
+                with self.lock:
+                    self.second_copies += 1
+                    self.downloaded += size - prefix
+            data = jpeg_file(h, w, 75, scan)
+            with open(path, "wb") as f:
+                f.write(data)
+        except Exception as e:
+            raise RuntimeError(f"image_io: {os.path.basename(path)}: could not be written: {e}") from e
+
+    def _kind(self, path):
+        name = str(path).lower()
+        if self.png == "device" and name.endswith(".png"):
+            return "png"
+        if self.jpeg == "device" and name.endswith(_JPEG_NAMES):
+            return "jpeg"
+        return None
+
     def retire(self):
         """wait for the oldest batch in flight; False when there is none"""
         if not self.inflight:
@@ -657,33 +847,60 @@ class _Writer:
         slot = self.count % self.depth
         self.count += 1
         n = q.numel()
-        on_device = [self.png == "device" and str(p).lower().endswith(".png") for p in paths]
-        buf = None
-        if any(on_device):                                       # the whole batch: its other images' slots are not used
+        kinds = [self._kind(p) for p in paths]
+        buf = jbuf = None
+        if "png" in kinds:                                       # the whole batch: its other images' slots are not used
             buf, streams, _ = _png_zlib(_images_u8(q, "image_io"), PNG_FILTERS.index("adaptive"), 32768)
             head, capacity = buf.numel() - streams.numel(), streams.shape[1]
             if self.host_png[slot] is None or self.host_png[slot].numel() < buf.numel():
                 self.host_png[slot] = torch.empty(buf.numel(), dtype=torch.uint8, pin_memory=True)
             host_png = self.host_png[slot]
-        if not all(on_device) and (self.host[slot] is None or self.host[slot].numel() < n):
+        if "jpeg" in kinds:
+            jbuf, jstreams, _ = _jpeg_scan(_images_u8(q, "image_io"), 75)
+            jhead, jcap = jbuf.numel() - jstreams.numel(), jstreams.shape[1]
+            prefix = min(jcap, -(-int(self.jpeg_prefix * 3 * h * w) // 4096) * 4096)
+            if self.host_jpeg[slot] is None or self.host_jpeg[slot].numel() < jhead + B * prefix:
+                self.host_jpeg[slot] = torch.empty(jhead + B * prefix, dtype=torch.uint8, pin_memory=True)
+            host_jpeg = self.host_jpeg[slot]
+        pillow = None in kinds
+        if pillow and (self.host[slot] is None or self.host[slot].numel() < n):
             self.host[slot] = torch.empty(n, dtype=torch.uint8, pin_memory=True)
         host = self.host[slot]
         ready = torch.cuda.Event()
         ready.record()                                           # q (and its streams) are complete here on the current stream
         self.down.wait_event(ready)
+        got = 0
         with torch.cuda.stream(self.down):
-            if not all(on_device):
+            if pillow:
                 host[:n].view(B, h, w, 3).copy_(q, non_blocking=True)
+                got += n
             if buf is not None:
                 host_png[:buf.numel()].copy_(buf, non_blocking=True)
+                got += buf.numel()
+            if jbuf is not None:                                 # the sizes travel with the first prefix
+                host_jpeg[:jhead + prefix].copy_(jbuf[:jhead + prefix], non_blocking=True)
+                for k in range(1, B):
+                    if kinds[k] == "jpeg":
+                        host_jpeg[jhead + k * prefix:jhead + (k + 1) * prefix].copy_(
+                            jbuf[jhead + k * jcap:jhead + k * jcap + prefix], non_blocking=True)
+                got += jhead + prefix * (1 + sum(kd == "jpeg" for kd in kinds[1:]))
         q.record_stream(self.down)
-        if buf is not None:
-            buf.record_stream(self.down)
+        for t in (buf, jbuf):
+            if t is not None:
+                t.record_stream(self.down)
         done = torch.cuda.Event()
         done.record(self.down)
-        futures = [self.pool.submit(self._save_png, done, host_png, head, capacity, k, h, w, p) if dev
-                   else self.pool.submit(self._save, done, host, k, h, w, p) for k, (p, dev) in enumerate(zip(paths, on_device))]
-        self.inflight.append((futures, on_done, (q, buf)))
+        with self.lock:
+            self.downloaded += got
+        futures = []
+        for k, (p, kind) in enumerate(zip(paths, kinds)):
+            if kind == "png":
+                futures.append(self.pool.submit(self._save_png, done, host_png, head, capacity, k, h, w, p))
+            elif kind == "jpeg":
+                futures.append(self.pool.submit(self._save_jpeg, done, host_jpeg, jbuf, jhead, jcap, prefix, k, h, w, p))
+            else:
+                futures.append(self.pool.submit(self._save, done, host, k, h, w, p))
+        self.inflight.append((futures, on_done, (q, buf, jbuf)))
 
     def close(self):
         try:
@@ -706,7 +923,8 @@ class EnhanceReport:
     each launch), seconds: {"wall": the call, "wait_for_slot": of it, the main thread waiting for a batch in flight to
     finish so that its buffers come free}, tiles: with tile=, the number of tiles of each image (empty otherwise), ensemble:
     the number of views each image was averaged over (1: none were built), png: who encoded the .png files ("pillow" or
-    "device")"""
+    "device"), jpeg: who encoded the .jpg / .jpeg files (likewise); with jpeg="device", jpeg_second_copies: the images whose
+    scan was longer than the downloaded prefix, and downloaded: the bytes the writer's copies brought to the host"""
     names: list = field(default_factory=list)
     sizes: list = field(default_factory=list)
     batches: list = field(default_factory=list)
@@ -714,6 +932,9 @@ class EnhanceReport:
     tiles: list = field(default_factory=list)
     ensemble: int = 1
     png: str = "pillow"
+    jpeg: str = "pillow"
+    jpeg_second_copies: int = 0
+    downloaded: int = 0
 
 
 class _Stage:
@@ -742,7 +963,8 @@ def _decode(stop, path, name, stage):
 @torch.no_grad()
 def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
                    alpha: float = 1.0, batch_size: int = 1, threads: int = 8, depth: int = 2, process_group=None, tile=None,
-                   overlap: int = 32, tile_batch: int = 8, ensemble: int = 1, png: str = "pillow") -> EnhanceReport:
+                   overlap: int = 32, tile_batch: int = 8, ensemble: int = 1, png: str = "pillow", jpeg: str = "pillow",
+                   jpeg_prefix: float = 0.25) -> EnhanceReport:
     """eval.py / demo.py for a folder: every image file of in_dir (metrics.folder_images: its files and order) is enhanced as
     enhance_u8 does and saved to out_dir/<same file name> by PIL in the format its extension names (the reference's
     output_img.save(output_folder + name[0])); out_dir is created.  Decoding, the device and encoding overlap (module
@@ -758,9 +980,14 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
     png: "pillow" -- every file is encoded by PIL.  "device" -- an output whose name ends in .png (any case) is encoded on the
     device (png_zlib_u8 behind egress: adaptive filters, Huffman coding, no LZ77) and only framed and written by its worker:
     the same pixels in another, valid PNG file, independent of batch_size, threads and depth; other extensions keep PIL.
-    report.png says which.  ValueError for another value, before a worker starts."""
+    report.png says which.  ValueError for another value, before a worker starts.
+    jpeg: "pillow" -- as above.  "device" -- an output whose name ends in .jpg or .jpeg (any case) is encoded on the device at
+    quality 75 (jpeg_scan_u8 behind egress) and only framed and written by its worker: the file is Pillow's own, byte for byte,
+    independent of batch_size, threads, depth and jpeg_prefix (the fraction of 3 h w bytes of each scan downloaded up front;
+    _Writer).  report.jpeg says which.  ValueError for another value, before a worker starts."""
     views = _check_ensemble(ensemble, tile)
     png = _check_png(png)
+    jpeg = _check_jpeg(jpeg)
     t_start = time.perf_counter()
     device = metrics._model_device(model)
     if device.type != "cuda":
@@ -777,7 +1004,7 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
         batch_size, tile_batch = 1, _tile_batch(tile_batch)
     workers = max(1, min(int(threads), 16))
     mine = list(shard(len(files), rank, world))
-    report = EnhanceReport(names=[files.names[i] for i in mine], ensemble=int(ensemble), png=png)
+    report = EnhanceReport(names=[files.names[i] for i in mine], ensemble=int(ensemble), png=png, jpeg=jpeg)
     os.makedirs(out_dir, exist_ok=True)
     if not mine:
         report.seconds = {"wall": time.perf_counter() - t_start, "wait_for_slot": 0.0}
@@ -785,7 +1012,7 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
 
     stop = threading.Event()
     decoders = cf.ThreadPoolExecutor(max_workers=workers, thread_name_prefix="cidnet-decode")
-    writer = _Writer(device, workers, depth, png=png)
+    writer = _Writer(device, workers, depth, png=png, jpeg=jpeg, jpeg_prefix=jpeg_prefix)
     # depth batches in flight + the batch being formed + the image _plan looks ahead
     free = [_Stage() for _ in range((depth + 1) * batch_size + 1)]
     pending = collections.deque()                                # decodes submitted, not yet consumed: (position, stage, future)
@@ -860,4 +1087,5 @@ def enhance_folder(model, in_dir, out_dir, gamma: float = 1.0, gated: bool = Fal
         stop.set()
         decoders.shutdown(wait=True, cancel_futures=True)
     report.seconds = {"wall": time.perf_counter() - t_start, "wait_for_slot": writer.waited}
+    report.jpeg_second_copies, report.downloaded = writer.second_copies, writer.downloaded
     return report

@@ -358,7 +358,7 @@ def _plan(sizes, rank, world, batch_size):
 
 @torch.no_grad()
 def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, alpha, gamma, batch_size, process_group,
-              save_dir=None, run_key=None, ensemble=1, png="pillow"):
+              save_dir=None, run_key=None, ensemble=1, png="pillow", jpeg="pillow"):
     """The evaluation loop of evaluate() and evaluate_unpaired(), `who` / `noun` naming them in errors.  load(i, item, device)
     -> (input fp32 (3,h,w), what score needs of the image); trans_attrs: the model.trans attributes set for the run; score(q
     uint8 (B,3,h,w), [load's second values]) -> one (B,) fp64 device tensor per key; result(alpha=, per_image=, names=,
@@ -367,10 +367,12 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
     run_key(load's second value): what, beside the crop size, the samples of one score() call must share.
     ensemble: 1, or 2 / 4 / 8 -- the model runs on the views of the padded input, once per view group, and the merged fp32
     result (image_io.ensemble_views / ensemble_merge) stands where the model's output stood.
-    png: "pillow", or "device" -- save_dir's .png files carry a stream encoded on the device (image_io._Writer)."""
+    png: "pillow", or "device" -- save_dir's .png files carry a stream encoded on the device (image_io._Writer).
+    jpeg: "pillow", or "device" -- save_dir's .jpg / .jpeg files are encoded on the device, byte-equal to Pillow's."""
     from . import image_io                                       # image_io imports this module
     na, nb = image_io._check_ensemble(ensemble)
     png = image_io._check_png(png)
+    jpeg = image_io._check_jpeg(jpeg)
     device = _model_device(model)
     if not device.type == "cuda":
         raise RuntimeError(_NO_CPU)
@@ -395,7 +397,7 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
         os.makedirs(save_dir, exist_ok=True)
         file_names = getattr(items, "names", None)
         with torch.cuda.device(device):
-            writer = image_io._Writer(device, threads=8, depth=2, png=png)
+            writer = image_io._Writer(device, threads=8, depth=2, png=png, jpeg=jpeg)
 
     def sizes():
         for i in range(rank, n, world):
@@ -462,7 +464,7 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
 
 def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
              alpha=1.0, batch_size: int = 1, process_group=None, save_dir=None, resize: bool = False, ensemble: int = 1,
-             png: str = "pillow"):
+             png: str = "pillow", jpeg: str = "pillow"):
     """eval.py + measure.py on the device.  `pairs`: a sequence of (low, gt) -- low a (3,h,w) float image in [0, 1] (or a
     uint8 HWC image, converted as ToTensor() does), gt uint8 HWC / CHW or a float ToTensor() image of the same size
     (folder_pairs() yields these).  Each input is reflect-padded to a multiple of 8, run through model(pow(x, gamma)) in eval
@@ -481,6 +483,8 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     png: "pillow" -- every file is encoded by PIL.  "device" -- a name ending in .png gets a file whose IDAT stream was encoded
     on the device (image_io.png_zlib_u8: filters and Huffman coding, no LZ77): the same pixels in another, valid file; other
     extensions keep PIL.  The scores are untouched.  Any other value is a ValueError before anything runs.
+    jpeg: "pillow" -- as above.  "device" -- a name ending in .jpg or .jpeg (any case) gets the file Pillow would write at
+    quality 75, byte for byte, encoded on the device (image_io.jpeg_scan_u8).  The scores are untouched.
     resize: False -- a ground truth whose size differs from its input's is a ValueError.  True -- such a pair is scored as
     measure.py:133-134 scores it: the quantized output is resized to the ground truth's size (resize_u8: Pillow >= 7's default
     bicubic, byte for byte; per alpha of a sweep) and GT mean, PSNR and SSIM are taken from the resized image; the pairs'
@@ -517,7 +521,7 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     return _evaluate("evaluate", "image pairs", model, pairs, load,
                      dict(gated=bool(gated), alpha_s=float(alpha_s), gated2=bool(gated2)), score,
                      _KEYS + ("resized",) if resize else _KEYS, result, alpha, gamma, batch_size, process_group, save_dir,
-                     run_key=(lambda g: tuple(g.shape[-2:])) if resize else None, ensemble=ensemble, png=png)
+                     run_key=(lambda g: tuple(g.shape[-2:])) if resize else None, ensemble=ensemble, png=png, jpeg=jpeg)
 
 
 # ---- folder pairing (the one piece of host / disk code) ------------------------------------------------------------
@@ -1000,7 +1004,7 @@ class UnpairedResult:
 
 def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batch_size: int = 1, process_group=None,
                       save_dir=None, ensemble: int = 1, loe: bool = False, loe_sample=50, file_roundtrip: bool = False,
-                      jpeg_quality: int = 75, png: str = "pillow"):
+                      jpeg_quality: int = 75, png: str = "pillow", jpeg: str = "pillow"):
     """eval.py --unpaired + measure_niqe_bris.py on the device.  `images`: a sequence of (3,h,w) float images in [0, 1] (or
     uint8 HWC images, converted as ToTensor() does; folder_images() yields these), each at least 96 x 96.  Each is reflect-
     padded to a multiple of 8, run through model(pow(x, gamma)) in eval mode under no_grad with trans.gated2 = True and
@@ -1012,6 +1016,7 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
     Data-parallel as evaluate(): rank r scores images i % world == r, one SUM all-reduce gathers the values.
     save_dir: as evaluate() -- the enhanced images are also written there, under images.names[i] or "<i as 5 digits>.png".
     png: as evaluate() -- "device" writes save_dir's .png files from a stream encoded on the device; the scores are untouched.
+    jpeg: as evaluate() -- "device" writes save_dir's .jpg / .jpeg files from the device, byte-equal to Pillow's at quality 75.
     ensemble: as evaluate() -- 2, 4 or 8 views of the padded input, the merged result scored.
     loe: True -- each output is also scored with LOE (loe(), sampler loe_sample) against its input as supplied: to_uint8 of the
     fp32 input before the reflect pad and before ** gamma.  UnpairedResult.loe is the mean, per_image["loe"] the values; NIQE is
@@ -1058,7 +1063,7 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
         return UnpairedResult(per_image=per_image, ensemble=int(ensemble), **kw)
     return _evaluate("evaluate_unpaired", "images", model, images, load, dict(gated2=True), score,
                      ("niqe", "loe") if loe else ("niqe",), result, alpha,
-                     gamma, batch_size, process_group, save_dir, ensemble=ensemble, png=png)
+                     gamma, batch_size, process_group, save_dir, ensemble=ensemble, png=png, jpeg=jpeg)
 
 
 class FolderImages:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 21
+#define CIDNET_ABI_VERSION 22
 
 int cidnet_abi_version(void);
 
@@ -768,6 +768,43 @@ int cidnet_png_plan(int h, int w, int segment_bytes, long* out, int n);
 int cidnet_png_code_lengths(const unsigned* freq, int n, int maxbits, uint8_t* lens);
 int cidnet_png_encode_u8(const uint8_t* src, long src_stride, uint8_t* dst, long dst_stride, long long* sizes, void* ws,
                          long ws_bytes, int B, int h, int w, int filter, int segment_bytes, void* stream);
+
+/* ---- JPEG files written from the device (csrc/jpegenc.hip, csrc/jpeg_codes.h, csrc/jpeg_front.h, DESIGN.md 6.13;
+ * tests/jpegenc_ref.py restates the scan and tests/test_jpegenc_cpu.py pins the restatement to Pillow).  src: B interleaved
+ * (h,w,3) uint8 images, image b at src + b * src_stride (>= 3 h w, any byte alignment) -> slot b at dst + b * dst_stride: the
+ * entropy-coded scan -- the bytes between the SOS segment and the EOI marker -- of the file Pillow's Image.save(f, 'JPEG',
+ * quality=q) writes of the image at its defaults (baseline, 4:2:0, the Annex K Huffman tables, no restart markers), BYTE FOR
+ * BYTE; sizes[b] bytes of it (int64), the rest of the slot's first `capacity` bytes zero.  The host adds the 623 bytes of
+ * framing in front (SOI, APP0, two DQT, SOF0, four DHT, SOS) and the EOI behind (hvi-cidnet_amd/image_io.py: jpeg_file).
+ *   Coefficients: those of cidnet_metric_jpeg_roundtrip_u8 before its dequantise step, sign(v) ((|v| + 4 t) / (8 t)): the same
+ *   colour conversion, edge replication, h2v2 downsampling, forward DCT and exact division.  qtab: the 256 int32 of
+ *   jpeg_quant_plan on the device, as there.
+ *   Scan: one interleaved scan, MCUs in raster order over ceil(h/16) x ceil(w/16), in each the blocks Y(0,0) Y(0,1) Y(1,0)
+ *   Y(1,1) Cb Cr.  A luma block outside ceil(h/8) x ceil(w/8) blocks is a DUMMY (libjpeg transforms none there): all AC zero,
+ *   DC that of the block before it -- difference 0 and end of block, the six bits 00 1010, the predictor untouched.
+ *   DC: one predictor per component, 0 at the start, through the whole image; diff = DC - pred, s = bit length of |diff|
+ *   (0..11): the DC table's code of s, then the low s bits of diff, of diff - 1 when negative.  AC, zigzag 1..63: for v != 0
+ *   after `run` zeros, run >> 4 ZRL codes (0xF0), the code of ((run & 15) << 4) | s, then s bits of v (v - 1 when negative);
+ *   the end of block (0x00) when coefficient 63 is zero, nothing otherwise.  Bits MSB first; every 0xFF byte is followed by
+ *   0x00; the last partial byte is filled with 1-bits (and stuffed if that makes 0xFF).
+ * ws: B * plan[5] bytes, 16-byte aligned.  dst 4-byte aligned, dst_stride a multiple of 4 and >= the plan's capacity; sizes
+ * 8-byte aligned; qtab 4-byte aligned.  Nothing outside the first `capacity` bytes of the B slots, sizes[0..B) and the workspace
+ * is written.  Integer arithmetic only; the only atomics are integer ORs and adds whose result does not depend on their order:
+ * the bytes are identical from call to call and independent of the rest of the batch.  No host synchronisation; six launches,
+ * none of which waits for another workgroup (the bit offsets come from counts, a scan by one workgroup per image, then
+ * emission at known offsets).  Widths below 5 are accepted: the round trip's limit belongs to the decoder.
+ * CIDNET_ERR_ARG, before any launch: a NULL pointer, B, h or w < 1, a slot below the capacity, a misaligned dst / dst_stride /
+ *   ws / sizes / qtab, src_stride < 3 h w.  CIDNET_ERR_WS: a short workspace.  CIDNET_ERR_SHAPE: h or w > 65500 (no such file
+ *   exists), more than 2^22 MCUs, B > 65535.
+ * plan: host only, launches nothing; the function the launcher itself calls.  out[0..8] = MCU columns, MCU rows, luma block
+ *   columns ceil(w/8), luma block rows ceil(h/8), dummy blocks, workspace bytes per image, the capacity of one slot, the number
+ *   of partial sums of the bit-offset scan (groups of 16 MCUs), workgroups of the first launch per image.  The capacity is a
+ *   proven bound on the scan's size, a multiple of 4: a real block is at most 22 + 63 * 26 = 1660 bits, a dummy 6; the bytes
+ *   of that many bits, doubled for stuffing, + 2 (the proof is with jpegenc_plan in csrc/jpegenc.hip).  out NULL or n < 9 is
+ *   CIDNET_ERR_ARG and nothing is written; never writes past out[8]; the size errors are those above. */
+int cidnet_jpeg_encode_plan(int h, int w, long* out, int n);
+int cidnet_jpeg_encode_u8(const uint8_t* src, long src_stride, uint8_t* dst, long dst_stride, long long* sizes,
+                          void* ws, long ws_bytes, const int* qtab, int B, int h, int w, void* stream);
 
 /* ---- Tiled enhancement of one large image (hvi-cidnet_amd/image_io.py: tile_plan): the same two conversions seen through
  * overlapping windows of one fixed shape (th, tw), both multiples of 4.  The reference has no such mode; the contract is "the

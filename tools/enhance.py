@@ -46,6 +46,8 @@ def main(argv=None):
     ap.add_argument("--tile_batch", type=int, default=8, help="tiles per model launch")
     ap.add_argument("--ensemble", type=int, choices=(1, 2, 4, 8), default=1, help="views averaged per image (default 1: none)")
     ap.add_argument("--png", choices=("pillow", "device"), default="pillow", help="who encodes .png outputs (default pillow)")
+    ap.add_argument("--jpeg", choices=("pillow", "device"), default="pillow",
+                    help="who encodes .jpg / .jpeg outputs (default pillow; device writes the same bytes)")
     a = ap.parse_args(argv)
     if a.ensemble != 1 and a.tile is not None:
         ap.error("--ensemble and --tile cannot be combined")
@@ -68,13 +70,13 @@ def main(argv=None):
         sys.exit(f"no image file (.png .jpg .bmp .JPG .jpeg) in {a.input}")
     rep = P.enhance_folder(model, files, a.output_dir, gamma=a.gamma, gated=a.gated, alpha_s=a.alpha_s, gated2=a.gated2,
                            alpha=a.alpha_i, batch_size=a.batch_size, threads=a.threads, depth=a.depth, tile=a.tile,
-                           overlap=a.tile_overlap, tile_batch=a.tile_batch, ensemble=a.ensemble, png=a.png)
+                           overlap=a.tile_overlap, tile_batch=a.tile_batch, ensemble=a.ensemble, png=a.png, jpeg=a.jpeg)
     wall = rep.seconds["wall"]
     print(json.dumps({"what": "enhance", "input": a.input, "output_dir": a.output_dir, "variant": a.variant, "images": len(rep.names),
                       "batches": len(rep.batches), "seconds": rep.seconds, "images_per_s": len(rep.names) / wall if wall > 0 else None,
                       "missing_keys": missing, "unexpected_keys": unexpected, "names": rep.names,
                       "sizes": [list(s) for s in rep.sizes], "tile": a.tile, "tiles": rep.tiles, "ensemble": rep.ensemble,
-                      "png": rep.png}))
+                      "png": rep.png, "jpeg": rep.jpeg, "jpeg_second_copies": rep.jpeg_second_copies}))
 
 
 if __name__ == "__main__":
