@@ -8,7 +8,10 @@ also writes the files eval.py writes (image_io's egress kernel and writer), whic
     p = M.psnr(q, gt_u8, gt_mean=False)     # (B,) float64 on the device, no host synchronisation
     s = M.ssim(q, gt_u8, gt_mean=False)     # (B,) float64 on the device
     res = M.evaluate(model, pairs, gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0, batch_size=1, save_dir=None,
-                     resize=False)
+                     resize=False, lpips=None)
+    prm = M.load_lpips_params(alexnet_path, heads_path)       # torchvision's AlexNet state dict + lpips' alex.pth (not shipped)
+    d = M.lpips(q, gt_u8, prm, gt_mean=False)                 # (B,) float64 on the device: lpips.LPIPS(net='alex')
+    f = M.lpips_features(q, prm)                              # the five fp32 taps; M.lpips_layers: the five layer terms (B,5)
     pairs = M.folder_pairs(low_dir, high_dir)
     pairs = M.nested_folder_pairs(low_root, high_root, gt="name")      # LOL-Blur / SID: one sub-folder per scene
     per_folder, overall = M.group_means(res, pairs)
@@ -34,7 +37,7 @@ and the file round trip of the .jpg sets (eval.py saves such an output as a JPEG
     r = M.jpeg_roundtrip_u8(q, quality=75)          # uint8 (B,3,h,w) -> what PIL's save(.., 'JPEG') + open() returns, byte for byte
     res = M.evaluate_unpaired(model, images, prm, file_roundtrip=True)      # .jpg / .jpeg names scored as their decoded files
 
-The kernels are csrc/metrics.hip, csrc/resize.hip, csrc/niqe.hip, csrc/loe.hip and csrc/jpeg.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
+The kernels are csrc/metrics.hip, csrc/lpips.hip, csrc/resize.hip, csrc/niqe.hip, csrc/loe.hip and csrc/jpeg.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
 Differences from the reference scripts, none of which changes a per-image value:
   * measure.py counts a low image without a ground truth in the divisor of its averages (it skips the image after
     `n += 1`); here such an image is skipped and reported (FolderPairs.skipped, EvalResult.skipped) and not counted;
@@ -43,7 +46,9 @@ Differences from the reference scripts, none of which changes a per-image value:
   * a ground truth whose size differs from the output raises unless evaluate(resize=True) is asked for; then the quantized
     output is resized as measure.py:133-134 resizes it (resize_u8: Pillow >= 7's default filter, byte for byte);
   * PSNR sums its squared errors exactly (fp64) where measure.py averages in fp32: < 1e-4 dB apart;
-  * LPIPS is not computed (it needs AlexNet weights and the lpips package's heads);
+  * LPIPS (lpips(), evaluate(lpips=)) needs torchvision's AlexNet weights and the lpips package's heads,
+    which are not shipped: pass their paths (load_lpips_params); its layer distances are summed in fp64 from the fp32
+    features where the lpips package stays in fp32;
   * NIQE: the half-size image sums its 8 taps in fp64 and rounds once per pass where the reference sums them in fp32 (two
     fp32 ulps apart at most), and the block moments are summed in fp64 where the reference's are fp32 means; an image with
     fewer than two NaN-free blocks scores NaN (the reference raises from inside the SVD); BRISQUE is not computed; and by
@@ -53,6 +58,7 @@ Differences from the reference scripts, none of which changes a per-image value:
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import math
 import os
 import warnings
@@ -294,9 +300,12 @@ class EvalResult:
     skipped: list = field(default_factory=list)       # low images without a ground truth (folder_pairs)
     resized: list = field(default_factory=list)       # indices of the pairs whose output was resized to the ground truth's size
     ensemble: int = 1                                 # the number of views each output was averaged over (evaluate(ensemble=))
+    lpips: float = float("nan")                       # evaluate(lpips=): the means of per_image["lpips"] / ["lpips_gt_mean"]
+    lpips_gt_mean: float = float("nan")
 
 
 _KEYS = ("psnr", "ssim", "psnr_gt_mean", "ssim_gt_mean")
+_LPIPS_KEYS = ("lpips", "lpips_gt_mean")
 
 
 def _model_device(model):
@@ -464,7 +473,7 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
 
 def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
              alpha=1.0, batch_size: int = 1, process_group=None, save_dir=None, resize: bool = False, ensemble: int = 1,
-             png: str = "pillow", jpeg: str = "pillow"):
+             png: str = "pillow", jpeg: str = "pillow", lpips=None):
     """eval.py + measure.py on the device.  `pairs`: a sequence of (low, gt) -- low a (3,h,w) float image in [0, 1] (or a
     uint8 HWC image, converted as ToTensor() does), gt uint8 HWC / CHW or a float ToTensor() image of the same size
     (folder_pairs() yields these).  Each input is reflect-padded to a multiple of 8, run through model(pow(x, gamma)) in eval
@@ -493,7 +502,21 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     ensemble: 2, 4 or 8 -- geometric self-ensemble as image_io.enhance_u8(ensemble=) runs it: the model on the views of the
     padded input, once per view group (with a sweep: the trunk once per group, PHVIT once per value and group), and the merged
     fp32 result is what is quantized, saved and resized.  1: no view is built.  Any other value is a ValueError.
+    lpips: None -- PSNR and SSIM only, nothing else runs.  An LpipsParams, or (alexnet path, heads path) -- every pair is also
+    scored with lpips() without and with the GT-mean rescale, from the image PSNR and SSIM are taken from (the resized one
+    under resize=True, the merged one under ensemble=, per value of a sweep): EvalResult.lpips / .lpips_gt_mean and
+    per_image["lpips"] / ["lpips_gt_mean"], gathered like the other keys.  A batch's ground truths go through the extractor
+    once, for both variants and every alpha; an image under 31 x 31 raises as lpips() does.
     The model's attributes and the train / eval mode of every submodule are restored afterwards."""
+    lp = None if lpips is None else _lpips_params(lpips)
+    gt_taps = [None, None]                          # the last batch's ground truths and their taps: shared by a sweep's values
+
+    def lpips_cols(q, g, gts):
+        if gt_taps[0] is None or len(gt_taps[0]) != len(gts) or any(a is not b for a, b in zip(gt_taps[0], gts)):
+            gt_taps[:] = [list(gts), None]
+        plain, gtm, gt_taps[1] = _lpips_both(q, g, lp, gt_taps[1])
+        return plain, gtm
+
     def load(i, pair, device):
         x, g = _image_f32(pair[0], device), _gt_u8(pair[1], device)
         if tuple(g.shape) != tuple(x.shape) and not resize:
@@ -505,12 +528,12 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     def score(q, gts):
         g = torch.stack(gts) if len(gts) > 1 else gts[0].unsqueeze(0)
         if not resize:
-            return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True))
+            return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True), *(lpips_cols(q, g, gts) if lp else ()))
         # the samples of a run share the ground truth's size (run_key); the flag column travels with the values, so that
         # every rank of a sharded evaluation reports the same indices
         flag = torch.full((q.shape[0],), float(q.shape[-2:] != g.shape[-2:]), dtype=torch.float64, device=q.device)
         q = resize_u8(q, g.shape[-2:])
-        return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True), flag)
+        return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True), *(lpips_cols(q, g, gts) if lp else ()), flag)
     skipped = list(getattr(pairs, "skipped", []))
 
     def result(per_image, **kw):
@@ -520,7 +543,8 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
                           ensemble=int(ensemble), **kw)
     return _evaluate("evaluate", "image pairs", model, pairs, load,
                      dict(gated=bool(gated), alpha_s=float(alpha_s), gated2=bool(gated2)), score,
-                     _KEYS + ("resized",) if resize else _KEYS, result, alpha, gamma, batch_size, process_group, save_dir,
+                     _KEYS + (_LPIPS_KEYS if lp else ()) + (("resized",) if resize else ()), result, alpha, gamma, batch_size,
+                     process_group, save_dir,
                      run_key=(lambda g: tuple(g.shape[-2:])) if resize else None, ensemble=ensemble, png=png, jpeg=jpeg)
 
 
@@ -1086,3 +1110,229 @@ def folder_images(directory: str) -> FolderImages:
     names = sorted(f for f in os.listdir(directory)
                    if f.endswith(UNPAIRED_EXTENSIONS) and os.path.isfile(os.path.join(directory, f)))
     return FolderImages([os.path.join(directory, f) for f in names], names)
+
+
+# ---- LPIPS, AlexNet variant (measure.py:78,145-153 -> lpips.LPIPS(net='alex')) ------------------------------------------
+LPIPS_MIN = 31
+# (index in torchvision's AlexNet `features`, out channels, in channels, kernel, stride, padding, pooled first)
+LPIPS_LAYERS = ((0, 64, 3, 11, 4, 2, False), (3, 192, 64, 5, 1, 2, True), (6, 384, 192, 3, 1, 1, True),
+                (8, 256, 384, 3, 1, 1, False), (10, 256, 256, 3, 1, 1, False))
+_LPIPS_NO_PARAMS = ("LPIPS needs torchvision's AlexNet weights and the lpips package's alex.pth heads: pass an LpipsParams or "
+                    "the pair of paths (load_lpips_params); neither file is shipped with this package")
+
+
+@dataclass(frozen=True)
+class LpipsParams:
+    """The frozen parameters of lpips.LPIPS(net='alex'): per tap the convolution's weight (M,C,k,k) and bias (M), fp32 host
+    tensors in torchvision's shapes, and the 1x1 head as a (C_l,) fp32 tensor.  on(device) uploads them once per device."""
+    weights: tuple
+    biases: tuple
+    heads: tuple
+    _dev: dict = field(default_factory=dict, repr=False, compare=False)      # device index -> (weights, biases, heads) there
+
+    def __post_init__(self):
+        for name, got, want in _lpips_shapes(self.weights, self.biases, self.heads):
+            if got != want:
+                raise ValueError(f"LpipsParams: {name} has shape {got}, expected {want}")
+
+    def on(self, device):
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        if key not in self._dev:
+            self._dev[key] = tuple(tuple(t.to(device, torch.float32).contiguous() for t in ts)
+                                   for ts in (self.weights, self.biases, self.heads))
+        return self._dev[key]
+
+    @staticmethod
+    def random(seed: int = 19) -> "LpipsParams":
+        """Deterministic stand-ins for tests and benchmarks: convolutions He-uniform with bound sqrt(6 / (k k C_in)), biases
+        uniform in +-0.05, heads uniform in [0, 2 / C).  These are NOT the trained metric: scores computed with them mean
+        nothing outside tests -- the real parameters come from load_lpips_params."""
+        gen = torch.Generator().manual_seed(int(seed))
+        ws, bs, hs = [], [], []
+        for _, m, c, k, _, _, _ in LPIPS_LAYERS:
+            bound = (6.0 / (k * k * c)) ** 0.5
+            ws.append((torch.rand((m, c, k, k), generator=gen) * 2 - 1) * bound)
+            bs.append((torch.rand(m, generator=gen) * 2 - 1) * 0.05)
+        for _, m, *_ in LPIPS_LAYERS:
+            hs.append(torch.rand(m, generator=gen) * (2.0 / m))
+        return LpipsParams(tuple(ws), tuple(bs), tuple(hs))
+
+
+def _lpips_shapes(weights, biases, heads):
+    if not (len(weights) == len(biases) == len(heads) == 5):
+        raise ValueError("LpipsParams: five weights, five biases and five heads are needed")
+    for l, (i, m, c, k, _, _, _) in enumerate(LPIPS_LAYERS):
+        yield f"weight {l}", tuple(weights[l].shape), (m, c, k, k)
+        yield f"bias {l}", tuple(biases[l].shape), (m,)
+        yield f"head {l}", tuple(heads[l].shape), (m,)
+
+
+def load_lpips_params(alexnet_path, heads_path) -> LpipsParams:
+    """Reads the two public files: torchvision's AlexNet state dict (keys features.{0,3,6,8,10}.{weight,bias}; the bare
+    {i}.weight form of a `features` state dict is accepted too) and the lpips package's weights/v0.1/alex.pth (keys
+    lin{0..4}.model.1.weight, (1,C,1,1)).  A missing key or a wrong shape is a ValueError that names it."""
+    if alexnet_path is None or heads_path is None:
+        raise ValueError(_LPIPS_NO_PARAMS)
+    sd = torch.load(alexnet_path, map_location="cpu", weights_only=True)
+    hd = torch.load(heads_path, map_location="cpu", weights_only=True)
+
+    def get(d, path, keys, shape):
+        for k in keys:
+            if k in d:
+                t = d[k]
+                if tuple(t.shape) != shape:
+                    raise ValueError(f"load_lpips_params: {k} in {path} has shape {tuple(t.shape)}, expected {shape}")
+                return t.detach().to(torch.float32).clone()
+        raise ValueError(f"load_lpips_params: {path} lacks {keys[0]}")
+    ws, bs, hs = [], [], []
+    for l, (i, m, c, k, _, _, _) in enumerate(LPIPS_LAYERS):
+        ws.append(get(sd, alexnet_path, (f"features.{i}.weight", f"{i}.weight"), (m, c, k, k)))
+        bs.append(get(sd, alexnet_path, (f"features.{i}.bias", f"{i}.bias"), (m,)))
+        hs.append(get(hd, heads_path, (f"lin{l}.model.1.weight",), (1, m, 1, 1)).reshape(m))
+    return LpipsParams(tuple(ws), tuple(bs), tuple(hs))
+
+
+def _lpips_params(params) -> LpipsParams:
+    if isinstance(params, LpipsParams):
+        return params
+    if isinstance(params, (tuple, list)) and len(params) == 2:
+        return load_lpips_params(*params)
+    raise ValueError(_LPIPS_NO_PARAMS)
+
+
+def lpips_feature_sizes(h: int, w: int):
+    """Host only -> the five (height, width) of the taps of an h x w image.  ValueError under 31 x 31: at 31 the first
+    convolution gives 7 and the pools 3 and then 1; anything smaller leaves a pool without a window."""
+    h, w = int(h), int(w)
+    if h < LPIPS_MIN or w < LPIPS_MIN:
+        raise ValueError(f"lpips needs images of at least {LPIPS_MIN} x {LPIPS_MIN} pixels (got {h} x {w}): a smaller one "
+                         "leaves AlexNet's second pool without a window")
+    out = (ctypes.c_int * 10)()
+    lib().call("cidnet_lpips_feature_sizes", h, w, out)
+    return [(out[2 * l], out[2 * l + 1]) for l in range(5)]
+
+
+def _lpips_input(q, what):
+    _on_device(q)
+    if q.dtype != torch.uint8:
+        raise RuntimeError(f"{what} takes uint8 images (got {q.dtype}); see to_uint8")
+    x = _batched(q, what)
+    lpips_feature_sizes(*x.shape[-2:])
+    return x
+
+
+def _lpips_scale(a, g):
+    """(B,) fp64 on the device: mean(gray(gt)) / mean(gray(restored)), the ratio psnr_ssim(gt_mean=True) forms"""
+    B, _, h, w = a.shape
+    n = lib().raw("cidnet_metric_lpips_scale_ws_floats")(B, h, w)
+    ws = torch.empty(n, dtype=torch.float32, device=a.device)
+    s = torch.empty(B, dtype=torch.float64, device=a.device)
+    lib().call("cidnet_metric_lpips_scale", ops._p(a), ops._p(g), ops._p(s), ops._p(ws), n, B, h, w, ops._stream())
+    return s
+
+
+def _lpips_extract(parts, prm):
+    """parts: [(uint8 (B_i,3,h,w), scale (B_i,) fp64 or None), ...] of one size -> the five fp32 taps of their concatenation,
+    one batch through the extractor.  The caller has made the device current."""
+    dev = parts[0][0].device
+    h, w = parts[0][0].shape[-2:]
+    N = sum(q.shape[0] for q, _ in parts)
+    L = lib()
+    x = torch.empty((N, 3, h, w), dtype=torch.float32, device=dev)
+    i = 0
+    for q, s in parts:
+        L.call("cidnet_metric_lpips_ingest", ops._p(q), ops._p(s), ops._p(x[i:]), q.shape[0], h, w, ops._stream())
+        i += q.shape[0]
+    weights, biases, _ = prm.on(dev)
+    feats, H, W = [], h, w
+    for l, (_, m, c, k, stride, pad, pooled) in enumerate(LPIPS_LAYERS):
+        if pooled:
+            Hp, Wp = (H - 3) // 2 + 1, (W - 3) // 2 + 1
+            y = torch.empty((N, c, Hp, Wp), dtype=torch.float32, device=dev)
+            L.call("cidnet_lpips_maxpool3s2", ops._p(x), ops._p(y), N * c, H, W, ops._stream())
+            x, H, W = y, Hp, Wp
+        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+        y = torch.empty((N, m, Ho, Wo), dtype=torch.float32, device=dev)
+        L.call("cidnet_lpips_conv_relu", ops._p(x), ops._p(weights[l]), ops._p(biases[l]), ops._p(y), N, m, c, H, W, k, stride,
+               pad, ops._stream())
+        feats.append(y)
+        x, H, W = y, Ho, Wo
+    return feats
+
+
+def _lpips_distance(f0, f1, prm, h, w, want_layers=True, want_score=True):
+    """f0, f1: the five taps of B images each (contiguous, a batch slice of _lpips_extract's result will do) of h x w images
+    -> (layers (B,5) fp64, score (B,) fp64)"""
+    dev = f0[0].device
+    B = f0[0].shape[0]
+    L = lib()
+    n = L.raw("cidnet_metric_lpips_ws_floats")(B, h, w)
+    ws = torch.empty(n, dtype=torch.float32, device=dev)
+    heads = prm.on(dev)[2]
+    for l in range(5):
+        _, C, fh, fw = f0[l].shape
+        L.call("cidnet_metric_lpips_layer", ops._p(f0[l]), ops._p(f1[l]), ops._p(heads[l]), ops._p(ws), n, l, B, C, fh, fw, h, w,
+               ops._stream())
+    layers = torch.empty((B, 5), dtype=torch.float64, device=dev) if want_layers else None
+    score = torch.empty(B, dtype=torch.float64, device=dev) if want_score else None
+    L.call("cidnet_metric_lpips_finish", ops._p(ws), n, ops._p(layers), ops._p(score), B, h, w, ops._stream())
+    return layers, score
+
+
+def lpips_features(q_u8: torch.Tensor, params, scale=None):
+    """uint8 (B,3,h,w) (or (3,h,w)) on the device -> the five fp32 taps [(B,64,.,.), (B,192,.,.), (B,384,.,.), (B,256,.,.),
+    (B,256,.,.)] of AlexNet on x = u / 127.5 - 1 behind lpips' scaling layer (include/cidnet_hip.h: LPIPS, steps 1-2).
+    scale: None, or (B,) fp64 on the device -- the image enters as the float clip(u * scale, 0, 255) (GT mean).
+    params: an LpipsParams or (alexnet path, heads path).  h, w >= 31."""
+    prm = _lpips_params(params)
+    x = _lpips_input(q_u8, "lpips_features")
+    if scale is not None:
+        _on_device(scale)
+        if scale.dtype != torch.float64 or tuple(scale.shape) != (x.shape[0],):
+            raise RuntimeError(f"lpips_features: scale must be ({x.shape[0]},) float64 (got {tuple(scale.shape)} {scale.dtype})")
+        scale = scale.contiguous()
+    with torch.cuda.device(x.device):
+        return _lpips_extract([(x, scale)], prm)
+
+
+def _lpips_pair(restored, gt, what):
+    a, g = _lpips_input(restored, what), _lpips_input(gt, what)
+    if a.shape != g.shape or a.device != g.device:
+        raise RuntimeError(f"{what}: restored {tuple(a.shape)} and gt {tuple(g.shape)} differ")
+    return a, g
+
+
+def _lpips_run(restored, gt, params, gt_mean, what, want_layers, want_score):
+    prm = _lpips_params(params)
+    a, g = _lpips_pair(restored, gt, what)
+    B, _, h, w = a.shape
+    with torch.cuda.device(a.device):
+        f = _lpips_extract([(a, _lpips_scale(a, g) if gt_mean else None), (g, None)], prm)
+        return _lpips_distance([t[:B] for t in f], [t[B:] for t in f], prm, h, w, want_layers, want_score)
+
+
+def lpips_layers(restored_u8: torch.Tensor, gt_u8: torch.Tensor, params, gt_mean: bool = False) -> torch.Tensor:
+    """uint8 (B,3,h,w) pairs on the device -> (B,5) float64 on the device: the five layer terms d_l whose sum is lpips()"""
+    return _lpips_run(restored_u8, gt_u8, params, gt_mean, "lpips_layers", True, False)[0]
+
+
+def lpips(restored_u8: torch.Tensor, gt_u8: torch.Tensor, params, gt_mean: bool = False) -> torch.Tensor:
+    """uint8 (B,3,h,w) pairs on the device -> (B,) float64 on the device, no host synchronisation: lpips.LPIPS(net='alex')
+    (version 0.1, lpips=True, spatial=False, eval mode) of each pair as measure.py:145-153 calls it.  gt_mean: `restored`
+    enters as the float clip(restored * s, 0, 255), s = mean(gray(gt)) / mean(gray(restored)) (measure.py:138-146).
+    Identical images score exactly 0; a result is bit-identical from call to call and independent of the rest of the batch.
+    params: an LpipsParams or (alexnet path, heads path).  h, w >= 31."""
+    return _lpips_run(restored_u8, gt_u8, params, gt_mean, "lpips", False, True)[1]
+
+
+def _lpips_both(q, g, prm, gt_feats=None):
+    """evaluate()'s LPIPS columns: (lpips, lpips_gt_mean, the ground truth's taps).  The restored and the rescaled images go
+    through the extractor as one batch; the ground truth's taps are computed unless handed in (an alpha sweep reuses them)."""
+    B, _, h, w = q.shape
+    lpips_feature_sizes(h, w)
+    if gt_feats is None:
+        gt_feats = _lpips_extract([(g, None)], prm)
+    f = _lpips_extract([(q, None), (q, _lpips_scale(q, g))], prm)
+    plain = _lpips_distance([t[:B] for t in f], gt_feats, prm, h, w, False, True)[1]
+    gtm = _lpips_distance([t[B:] for t in f], gt_feats, prm, h, w, False, True)[1]
+    return plain, gtm, gt_feats

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 22
+#define CIDNET_ABI_VERSION 23
 
 int cidnet_abi_version(void);
 
@@ -863,6 +863,55 @@ int cidnet_image_egress_tiles(const float* tiles, const int* origins_y, int ny, 
  * consecutive floats (csrc/ensemble.hip). */
 int cidnet_ensemble_views(const float* x, float* y, int B, int C, int H, int W, int first, int count, void* stream);
 int cidnet_ensemble_merge(const float* ya, int na, const float* yb, int nb, float* out, int B, int C, int H, int W, void* stream);
+
+/* ---- LPIPS, AlexNet variant (lpips.LPIPS(net='alex'), version 0.1, lpips=True, spatial=False, eval mode: measure.py:78,
+ * 145-153 of the reference), forward only (csrc/lpips.hip).  The definition, in the order the entries are used:
+ *  (1) ingest:  x = u / 127.5 - 1 formed in fp64 and rounded once to fp32, then the scaling layer in fp32,
+ *      (x - shift_c) / scale_c with shift = (-.030, -.088, -.188), scale = (.458, .448, .450).  u is the 8-bit value; with
+ *      scale != NULL (GT mean) the fp64 value clip(u * scale[b], 0, 255), which is not re-quantized (measure.py:138-146).
+ *  (2) features: five taps of torchvision's AlexNet `features`, each after its ReLU:
+ *      conv(3->64, 11x11, stride 4, pad 2) | maxpool(3, 2), conv(64->192, 5x5, pad 2) | maxpool(3, 2), conv(192->384, 3x3,
+ *      pad 1) | conv(384->256, 3x3, pad 1) | conv(256->256, 3x3, pad 1); every conv has a bias, sizes use floor, the pools
+ *      have no padding and are not ceil mode.
+ *  (3) per layer l: n(f) = f / (sqrt(sum_c f^2) + 1e-10) per pixel, d_l = mean over pixels of sum_c w_l[c] (n(f0) - n(f1))^2,
+ *      w_l the layer's 1x1 head (C_l -> 1, no bias); C_l = 64, 192, 384, 256, 256.
+ *  (4) score = sum_l d_l, one number per pair.
+ *  (5) the smallest image is 31 x 31 (feature maps 7, 3, 1, 1, 1); anything smaller is CIDNET_ERR_SHAPE.
+ * feature_sizes: host only.  sizes[2 l], sizes[2 l + 1] = height and width of tap l of an h x w image (step 2's floors);
+ *   CIDNET_ERR_SHAPE under 31 in either axis.
+ * scale: scale[b] = mean(gray(gt_b)) / mean(gray(restored_b)), the ratio cidnet_metric_psnr_ssim forms for GT mean (the same
+ *   exact integer sums and the same fp64 expression, so the same bits).  uint8 (B,3,h,w) inputs; ws: cidnet_metric_lpips_
+ *   scale_ws_floats(B, h, w) floats, 8-byte aligned.  B > 65535 is CIDNET_ERR_SHAPE.
+ * ingest: step 1.  q uint8 (B,3,h,w) planar, scale NULL or B doubles on the device -> x fp32 (B,3,h,w).
+ * conv_relu: y = relu(conv(x) + bias), x (B,C,H,W), w (M,C,ksize,ksize) contiguous, y (B,M,Ho,Wo) with Ho = floor((H + 2 pad -
+ *   ksize) / stride) + 1.  (ksize, stride, pad) is one of (11, 4, 2), (5, 1, 2), (3, 1, 1) and M a multiple of 64, else
+ *   CIDNET_ERR_SHAPE; also when the padded input is smaller than the window, B > 65535 or a tensor of one image has more than
+ *   2^31 - 1 elements.  An implicit GEMM on the fp32 matrix cores (fp32 products, fp32 accumulation: the accuracy of an fp32
+ *   convolution); the padding and the remainder of K = C ksize^2 are zeros written by the staging, never a read outside x or
+ *   w.  A block works on one image: an image's result does not depend on the rest of the batch.  All five layers of step 2.
+ * maxpool3s2: y (planes, floor((H - 3) / 2) + 1, floor((W - 3) / 2) + 1) = the maximum of each 3 x 3 window at stride 2 of
+ *   x (planes, H, W).  H < 3 or W < 3 is CIDNET_ERR_SHAPE.  A NaN in a window is skipped (fmaxf), where torch propagates it.
+ * layer: step 3 for tap `layer` (0..4) of B pairs: f0, f1 fp32 (B,C,fh,fw), head C floats -> block partials in ws.  (C, fh,
+ *   fw) must be what the layer has for an h x w image, else CIDNET_ERR_SHAPE.  fp64 from the fp32 features on: sums of
+ *   squares, norms (as a reciprocal, one fp64 rounding away from the quotient), weighted squared differences.  No fused
+ *   multiply-add: identical features give exactly 0.
+ * finish: step 3's mean and step 4: layers (B,5) and score (B) doubles (either may be NULL) from the partials all five layer
+ *   calls left in ws.  A fixed-order two-stage reduction (per-block partials in fixed slots, one wave per image sums them):
+ *   no atomics, bit-identical from call to call, independent of the rest of the batch.
+ *   ws: cidnet_metric_lpips_ws_floats(B, h, w) floats, 8-byte aligned, the same buffer for the five layer calls and finish;
+ *   the query is host only and returns 0 for an image under 31 x 31. */
+int cidnet_lpips_feature_sizes(int h, int w, int* sizes);
+long cidnet_metric_lpips_scale_ws_floats(int B, int h, int w);
+int cidnet_metric_lpips_scale(const uint8_t* restored, const uint8_t* gt, double* scale, float* ws, long ws_floats, int B, int h,
+                              int w, void* stream);
+int cidnet_metric_lpips_ingest(const uint8_t* q, const double* scale, float* x, int B, int h, int w, void* stream);
+int cidnet_lpips_conv_relu(const float* x, const float* w, const float* bias, float* y, int B, int M, int C, int H, int W, int ksize,
+                           int stride, int pad, void* stream);
+int cidnet_lpips_maxpool3s2(const float* x, float* y, long planes, int H, int W, void* stream);
+long cidnet_metric_lpips_ws_floats(int B, int h, int w);
+int cidnet_metric_lpips_layer(const float* f0, const float* f1, const float* head, float* ws, long ws_floats, int layer, int B, int C,
+                              int fh, int fw, int h, int w, void* stream);
+int cidnet_metric_lpips_finish(const float* ws, long ws_floats, double* layers, double* score, int B, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }
