@@ -22,7 +22,8 @@ What differs from the reference's loop:
   * left out: the per-epoch training/test.png dump of the step's own output (the validation's enhanced images can be written:
     val_args=dict(save_dir=...), metrics.evaluate), the metrics .md table (on_epoch hands the numbers to the caller), the
     option parser, the cyclic scheduler variant.  LPIPS is opt-in: val_args=dict(lpips=params or the two paths) adds
-    `lpips` (and `lpips_ema`) to the record (metrics.evaluate(lpips=)).
+    `lpips` (and `lpips_ema`) to the record (metrics.evaluate(lpips=)); so is the CIEDE2000 colour difference:
+    val_args=dict(ciede2000=True) adds `ciede2000` (and `ciede2000_ema`).
 The sets kept as one sub-folder per scene (SICE / SID / LOL-blur, data/SICE_blur_SID.py) train through the same loop:
 data.ResidentPairs.from_scene_folders and TrainBatches(sampling="scene") draw a scene, then one of its images; and a batch
 source that yields (x, gt, raw) -- TrainBatches(raw=True), the low image before `** gamma` -- has its third element handed to
@@ -88,7 +89,7 @@ def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, star
     Every `snapshots` epochs rank 0 writes, into out_dir, epoch_{epoch}.pth (the model's state_dict(), what the reference
     loads with strict=True) and epoch_{epoch}.train.pt (the trainer's state_dict(), the epoch, the position in the schedule
     and the arguments that fix it); then, when val_pairs is given, metrics.evaluate(model, val_pairs, **val_args) runs and
-    the record gains psnr / ssim, and lpips when val_args carries lpips= (val_args may carry save_dir: the scored images are then also written there, each
+    the record gains psnr / ssim, lpips when val_args carries lpips= and ciede2000 when it carries ciede2000=True (val_args may carry save_dir: the scored images are then also written there, each
     validation over the last one's files).
     Record: epoch, lr, steps, skipped, loss (mean over the applied steps, see epoch_stats; averaged over the ranks with one
     all-reduce per epoch), grad_norm_max, clipped (applied steps with coef < 1).  on_epoch(record) runs on every rank.
@@ -155,12 +156,16 @@ def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, star
                 rec["psnr"], rec["ssim"] = res.psnr, res.ssim
                 if (val_args or {}).get("lpips") is not None:
                     rec["lpips"] = res.lpips
+                if (val_args or {}).get("ciede2000"):
+                    rec["ciede2000"] = res.ciede2000
             if val_pairs is not None and val_weights in ("ema", "both"):
                 with trainer.ema_weights():
                     res = _validate(model, val_pairs, val_args, process_group)
                 rec["psnr_ema"], rec["ssim_ema"] = res.psnr, res.ssim
                 if (val_args or {}).get("lpips") is not None:
                     rec["lpips_ema"] = res.lpips
+                if (val_args or {}).get("ciede2000"):
+                    rec["ciede2000_ema"] = res.ciede2000
         records.append(rec)
         if on_epoch is not None:
             on_epoch(rec)

@@ -8,10 +8,12 @@ also writes the files eval.py writes (image_io's egress kernel and writer), whic
     p = M.psnr(q, gt_u8, gt_mean=False)     # (B,) float64 on the device, no host synchronisation
     s = M.ssim(q, gt_u8, gt_mean=False)     # (B,) float64 on the device
     res = M.evaluate(model, pairs, gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0, batch_size=1, save_dir=None,
-                     resize=False, lpips=None)
+                     resize=False, lpips=None, ciede2000=False)
     prm = M.load_lpips_params(alexnet_path, heads_path)       # torchvision's AlexNet state dict + lpips' alex.pth (not shipped)
     d = M.lpips(q, gt_u8, prm, gt_mean=False)                 # (B,) float64 on the device: lpips.LPIPS(net='alex')
     f = M.lpips_features(q, prm)                              # the five fp32 taps; M.lpips_layers: the five layer terms (B,5)
+    e = M.ciede2000(q, gt_u8, gt_mean=False)                  # (B,) float64 on the device: mean CIEDE2000 colour difference
+    m = M.ciede2000_map(q, gt_u8)                             # (B,h,w) float64; M.ciede2000_lab(lab1, lab2): dE00 of Lab pairs
     pairs = M.folder_pairs(low_dir, high_dir)
     pairs = M.nested_folder_pairs(low_root, high_root, gt="name")      # LOL-Blur / SID: one sub-folder per scene
     per_folder, overall = M.group_means(res, pairs)
@@ -37,7 +39,7 @@ and the file round trip of the .jpg sets (eval.py saves such an output as a JPEG
     r = M.jpeg_roundtrip_u8(q, quality=75)          # uint8 (B,3,h,w) -> what PIL's save(.., 'JPEG') + open() returns, byte for byte
     res = M.evaluate_unpaired(model, images, prm, file_roundtrip=True)      # .jpg / .jpeg names scored as their decoded files
 
-The kernels are csrc/metrics.hip, csrc/lpips.hip, csrc/resize.hip, csrc/niqe.hip, csrc/loe.hip and csrc/jpeg.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
+The kernels are csrc/metrics.hip, csrc/lpips.hip, csrc/ciede2000.hip, csrc/resize.hip, csrc/niqe.hip, csrc/loe.hip and csrc/jpeg.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
 Differences from the reference scripts, none of which changes a per-image value:
   * measure.py counts a low image without a ground truth in the divisor of its averages (it skips the image after
     `n += 1`); here such an image is skipped and reported (FolderPairs.skipped, EvalResult.skipped) and not counted;
@@ -49,6 +51,8 @@ Differences from the reference scripts, none of which changes a per-image value:
   * LPIPS (lpips(), evaluate(lpips=)) needs torchvision's AlexNet weights and the lpips package's heads,
     which are not shipped: pass their paths (load_lpips_params); its layer distances are summed in fp64 from the fp32
     features where the lpips package stays in fp32;
+  * CIEDE2000 (ciede2000(), evaluate(ciede2000=True)) has no counterpart in the reference: opt-in, the mean
+    dE00 between the output and the ground truth with scikit-image's sRGB -> Lab constants, in fp64;
   * NIQE: the half-size image sums its 8 taps in fp64 and rounds once per pass where the reference sums them in fp32 (two
     fp32 ulps apart at most), and the block moments are summed in fp64 where the reference's are fp32 means; an image with
     fewer than two NaN-free blocks scores NaN (the reference raises from inside the SVD); BRISQUE is not computed; and by
@@ -204,17 +208,23 @@ def resize_u8(q: torch.Tensor, size) -> torch.Tensor:
     return out[0] if squeeze else out
 
 
+def _u8_pair(who, restored, gt):
+    """the input checks of the paired metrics -> the two images as contiguous (B,3,h,w)"""
+    _on_device(restored, gt)
+    if restored.dtype != torch.uint8 or gt.dtype != torch.uint8:
+        raise RuntimeError(f"{who} take uint8 images (got {restored.dtype}, {gt.dtype}); see to_uint8")
+    a, g = _batched(restored, "restored"), _batched(gt, "gt")
+    if a.shape != g.shape or a.device != g.device:
+        raise RuntimeError(f"{who}: restored {tuple(a.shape)} and gt {tuple(g.shape)} differ")
+    return a, g
+
+
 def psnr_ssim(restored: torch.Tensor, gt: torch.Tensor, gt_mean: bool = False, want_psnr: bool = True,
               want_ssim: bool = True):
     """uint8 (B,3,h,w) pairs on the device -> (psnr, ssim), each (B,) float64 on the device (None where not wanted), from one
     pass over the images.  gt_mean: rescale `restored` by mean(gray(gt)) / mean(gray(restored)) first (measure.py:138-141),
     on the device.  SSIM needs h, w >= 11."""
-    _on_device(restored, gt)
-    if restored.dtype != torch.uint8 or gt.dtype != torch.uint8:
-        raise RuntimeError(f"psnr / ssim take uint8 images (got {restored.dtype}, {gt.dtype}); see to_uint8")
-    a, g = _batched(restored, "restored"), _batched(gt, "gt")
-    if a.shape != g.shape or a.device != g.device:
-        raise RuntimeError(f"psnr / ssim: restored {tuple(a.shape)} and gt {tuple(g.shape)} differ")
+    a, g = _u8_pair("psnr / ssim", restored, gt)
     B, _, h, w = a.shape
     if want_ssim and (h < 11 or w < 11):
         raise RuntimeError(f"ssim needs images of at least 11 x 11 pixels (got {h} x {w}): the 11 x 11 window's valid region "
@@ -302,6 +312,8 @@ class EvalResult:
     ensemble: int = 1                                 # the number of views each output was averaged over (evaluate(ensemble=))
     lpips: float = float("nan")                       # evaluate(lpips=): the means of per_image["lpips"] / ["lpips_gt_mean"]
     lpips_gt_mean: float = float("nan")
+    ciede2000: float = float("nan")                   # evaluate(ciede2000=True): the means of per_image["ciede2000"] / [.._gt_mean]
+    ciede2000_gt_mean: float = float("nan")
 
 
 _KEYS = ("psnr", "ssim", "psnr_gt_mean", "ssim_gt_mean")
@@ -473,7 +485,7 @@ def _evaluate(who, noun, model, items, load, trans_attrs, score, keys, result, a
 
 def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: float = 1.3, gated2: bool = False,
              alpha=1.0, batch_size: int = 1, process_group=None, save_dir=None, resize: bool = False, ensemble: int = 1,
-             png: str = "pillow", jpeg: str = "pillow", lpips=None):
+             png: str = "pillow", jpeg: str = "pillow", lpips=None, ciede2000: bool = False):
     """eval.py + measure.py on the device.  `pairs`: a sequence of (low, gt) -- low a (3,h,w) float image in [0, 1] (or a
     uint8 HWC image, converted as ToTensor() does), gt uint8 HWC / CHW or a float ToTensor() image of the same size
     (folder_pairs() yields these).  Each input is reflect-padded to a multiple of 8, run through model(pow(x, gamma)) in eval
@@ -507,6 +519,10 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     under resize=True, the merged one under ensemble=, per value of a sweep): EvalResult.lpips / .lpips_gt_mean and
     per_image["lpips"] / ["lpips_gt_mean"], gathered like the other keys.  A batch's ground truths go through the extractor
     once, for both variants and every alpha; an image under 31 x 31 raises as lpips() does.
+    ciede2000: False -- nothing of it runs and the result is what it was without the keyword.  True -- every pair is also scored
+    with ciede2000() (the mean CIEDE2000 colour difference; the reference has none) without and with the GT-mean
+    rescale, from the image PSNR and SSIM are taken from: EvalResult.ciede2000 / .ciede2000_gt_mean and per_image["ciede2000"] /
+    ["ciede2000_gt_mean"], after the LPIPS keys, gathered like the other keys.
     The model's attributes and the train / eval mode of every submodule are restored afterwards."""
     lp = None if lpips is None else _lpips_params(lpips)
     gt_taps = [None, None]                          # the last batch's ground truths and their taps: shared by a sweep's values
@@ -516,6 +532,9 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
             gt_taps[:] = [list(gts), None]
         plain, gtm, gt_taps[1] = _lpips_both(q, g, lp, gt_taps[1])
         return plain, gtm
+
+    def extra_cols(q, g, gts):                      # the opt-in columns, in key order
+        return (*(lpips_cols(q, g, gts) if lp else ()), *(_ciede_both(q, g) if ciede2000 else ()))
 
     def load(i, pair, device):
         x, g = _image_f32(pair[0], device), _gt_u8(pair[1], device)
@@ -528,12 +547,12 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     def score(q, gts):
         g = torch.stack(gts) if len(gts) > 1 else gts[0].unsqueeze(0)
         if not resize:
-            return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True), *(lpips_cols(q, g, gts) if lp else ()))
+            return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True), *extra_cols(q, g, gts))
         # the samples of a run share the ground truth's size (run_key); the flag column travels with the values, so that
         # every rank of a sharded evaluation reports the same indices
         flag = torch.full((q.shape[0],), float(q.shape[-2:] != g.shape[-2:]), dtype=torch.float64, device=q.device)
         q = resize_u8(q, g.shape[-2:])
-        return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True), *(lpips_cols(q, g, gts) if lp else ()), flag)
+        return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True), *extra_cols(q, g, gts), flag)
     skipped = list(getattr(pairs, "skipped", []))
 
     def result(per_image, **kw):
@@ -543,7 +562,8 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
                           ensemble=int(ensemble), **kw)
     return _evaluate("evaluate", "image pairs", model, pairs, load,
                      dict(gated=bool(gated), alpha_s=float(alpha_s), gated2=bool(gated2)), score,
-                     _KEYS + (_LPIPS_KEYS if lp else ()) + (("resized",) if resize else ()), result, alpha, gamma, batch_size,
+                     _KEYS + (_LPIPS_KEYS if lp else ()) + (_CIEDE_KEYS if ciede2000 else ()) + (("resized",) if resize else ()),
+                     result, alpha, gamma, batch_size,
                      process_group, save_dir,
                      run_key=(lambda g: tuple(g.shape[-2:])) if resize else None, ensemble=ensemble, png=png, jpeg=jpeg)
 
@@ -1336,3 +1356,89 @@ def _lpips_both(q, g, prm, gt_feats=None):
     plain = _lpips_distance([t[:B] for t in f], gt_feats, prm, h, w, False, True)[1]
     gtm = _lpips_distance([t[B:] for t in f], gt_feats, prm, h, w, False, True)[1]
     return plain, gtm, gt_feats
+
+
+# ---- CIEDE2000 (no counterpart in the reference) -----------------------------------------------------------
+_CIEDE_KEYS = ("ciede2000", "ciede2000_gt_mean")
+_ciede_tables_host = None
+_ciede_tables_dev = {}
+
+
+def ciede2000_tables() -> np.ndarray:
+    """(256,) fp64, host only: the linear value of every 8-bit sRGB level, v = level / 255, v > 0.04045 ? ((v + 0.055) /
+    1.055)^2.4 : v / 12.92 -- what the kernel reads where scikit-image's rgb2lab would call pow.  Read-only, cached."""
+    global _ciede_tables_host
+    if _ciede_tables_host is None:
+        v = np.arange(256, dtype=np.float64) / 255.0
+        t = np.where(v > 0.04045, np.power((v + 0.055) / 1.055, 2.4), v / 12.92)
+        t.setflags(write=False)
+        _ciede_tables_host = t
+    return _ciede_tables_host
+
+
+def _ciede_tables_on(device):
+    """uploaded once per process and device"""
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if key not in _ciede_tables_dev:
+        _ciede_tables_dev[key] = torch.from_numpy(ciede2000_tables().copy()).to(device)
+    return _ciede_tables_dev[key]
+
+
+def ciede2000_lab(lab1: torch.Tensor, lab2: torch.Tensor) -> torch.Tensor:
+    """fp64 (n,3) tensors of (L, a, b) on the device -> (n,) fp64 on the device: dE00 of each pair, lab1 as colour 1, by the
+    formulation of Sharma, Wu and Dalal (2005) with kL = kC = kH = 1 (include/cidnet_hip.h: CIEDE2000) -- the core of
+    ciede2000(), exposed so that it can be held against published Lab data."""
+    _on_device(lab1, lab2)
+    for t in (lab1, lab2):
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
+            raise RuntimeError(f"ciede2000_lab: expected fp64 (n,3) Lab values, got {t.dtype} {tuple(t.shape)}")
+    if lab1.shape != lab2.shape or lab1.device != lab2.device:
+        raise RuntimeError(f"ciede2000_lab: lab1 {tuple(lab1.shape)} and lab2 {tuple(lab2.shape)} differ")
+    a, b = lab1.contiguous(), lab2.contiguous()
+    out = torch.empty(a.shape[0], dtype=torch.float64, device=a.device)
+    if a.shape[0]:
+        with torch.cuda.device(a.device):
+            lib().call("cidnet_metric_ciede2000_lab", ops._p(a), ops._p(b), ops._p(out), a.shape[0], ops._stream())
+    return out
+
+
+def _ciede_launch(a, g, scale, want_map, want_mean):
+    """a, g: checked (B,3,h,w) uint8 pairs; scale: None or (B,) fp64 on the device -> (map or None, mean or None).  The caller
+    has made the device current."""
+    B, _, h, w = a.shape
+    L = lib()
+    n = L.raw("cidnet_metric_ciede2000_ws_bytes")(B, h, w)
+    ws = torch.empty(n, dtype=torch.uint8, device=a.device) if want_mean else None
+    dmap = torch.empty((B, h, w), dtype=torch.float64, device=a.device) if want_map else None
+    mean = torch.empty(B, dtype=torch.float64, device=a.device) if want_mean else None
+    L.call("cidnet_metric_ciede2000_u8", ops._p(a), ops._p(g), ops._p(scale), ops._p(_ciede_tables_on(a.device)), ops._p(dmap),
+           ops._p(mean), ops._p(ws), n, B, h, w, ops._stream())
+    return dmap, mean
+
+
+def _ciede_run(restored, gt, gt_mean, want_map, want_mean):
+    a, g = _u8_pair("ciede2000 / ciede2000_map", restored, gt)
+    with torch.cuda.device(a.device):
+        return _ciede_launch(a, g, _lpips_scale(a, g) if gt_mean else None, want_map, want_mean)
+
+
+def ciede2000_map(restored_u8: torch.Tensor, gt_u8: torch.Tensor, gt_mean: bool = False) -> torch.Tensor:
+    """uint8 (B,3,h,w) (or (3,h,w)) pairs on the device -> (B,h,w) fp64 on the device: dE00 of every pixel, see ciede2000()"""
+    return _ciede_run(restored_u8, gt_u8, gt_mean, True, False)[0]
+
+
+def ciede2000(restored_u8: torch.Tensor, gt_u8: torch.Tensor, gt_mean: bool = False) -> torch.Tensor:
+    """uint8 (B,3,h,w) (or (3,h,w)) pairs on the device -> (B,) fp64 on the device, no host synchronisation: the mean over the
+    pixels of the CIEDE2000 difference between `restored` (colour 1) and `gt` (colour 2), each converted sRGB -> Lab with
+    scikit-image's constants (D65 / 2 degree white) -- what deltaE_ciede2000(rgb2lab(a), rgb2lab(b)).mean() states, all in fp64
+    (the definition: include/cidnet_hip.h, CIEDE2000).  gt_mean: `restored` enters as the real number clip(restored * s, 0,
+    255), s = mean(gray(gt)) / mean(gray(restored)) as psnr_ssim(gt_mean=True) forms it, not re-quantized (measure.py:138-141);
+    an image whose gray mean is 0 gives whatever IEEE arithmetic makes of the infinite or NaN ratio.
+    Identical images score exactly 0; a fixed-order reduction: bit-identical from call to call and independent of the rest of
+    the batch (not bit-equal to ciede2000_map(...).mean(), which sums in another order).  Any h, w >= 1."""
+    return _ciede_run(restored_u8, gt_u8, gt_mean, False, True)[1]
+
+
+def _ciede_both(q, g):
+    """evaluate()'s CIEDE2000 columns of a checked batch: (plain, GT mean)"""
+    return _ciede_launch(q, g, None, False, True)[1], _ciede_launch(q, g, _lpips_scale(q, g), False, True)[1]

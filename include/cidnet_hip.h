@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 23
+#define CIDNET_ABI_VERSION 24
 
 int cidnet_abi_version(void);
 
@@ -912,6 +912,50 @@ long cidnet_metric_lpips_ws_floats(int B, int h, int w);
 int cidnet_metric_lpips_layer(const float* f0, const float* f1, const float* head, float* ws, long ws_floats, int layer, int B, int C,
                               int fh, int fw, int h, int w, void* stream);
 int cidnet_metric_lpips_finish(const float* ws, long ws_floats, double* layers, double* score, int B, int h, int w, void* stream);
+
+/* ---- CIEDE2000 colour difference (csrc/ciede2000.hip): the mean dE00 between the restored image (colour 1) and its ground
+ * truth (colour 2), the colour-fidelity number of the low-light literature, usually computed with scikit-image as
+ * deltaE_ciede2000(rgb2lab(a), rgb2lab(b)).mean().  The reference has none; the contract is this text.  All arithmetic fp64.
+ * sRGB -> Lab, scikit-image's constants: v = level / 255; lin = v > 0.04045 ? ((v + 0.055) / 1.055)^2.4 : v / 12.92;
+ *   XYZ = M lin, each row summed left to right, M = [[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169],
+ *   [0.019334, 0.119193, 0.950227]]; divided by the D65 / 2 degree white (0.95047, 1.0, 1.08883); f(t) = t > 0.008856 ? cbrt(t)
+ *   : 7.787 t + 16 / 116; L = 116 f(Y) - 16, a = 500 (f(X) - f(Y)), b = 200 (f(Y) - f(Z)).
+ * dE00, Sharma, Wu and Dalal (2005), kL = kC = kH = 1: C = hypot(a, b); Cbar = (C1 + C2) / 2; G = 0.5 (1 - sqrt(Cbar^7 /
+ *   (Cbar^7 + 25^7))); a' = (1 + G) a; C' = hypot(a', b); h' = atan2(b, a') in degrees, + 360 when negative (atan2(0, 0) = 0);
+ *   dL' = L2 - L1; dC' = C2' - C1'; dh' = 0 if C1' C2' = 0, else h2' - h1' brought into (-180, 180] by -360 when > 180 and + 360
+ *   when < -180; dH' = 2 sqrt(C1' C2') sin(dh' / 2); Lbar' = (L1 + L2) / 2; Cbar' = (C1' + C2') / 2; hbar' = h1' + h2' if C1' C2'
+ *   = 0, else (h1' + h2') / 2 if |h1' - h2'| <= 180, else (h1' + h2' + 360) / 2 if h1' + h2' < 360, else (h1' + h2' - 360) / 2;
+ *   T = 1 - 0.17 cos(hbar' - 30) + 0.24 cos(2 hbar') + 0.32 cos(3 hbar' + 6) - 0.20 cos(4 hbar' - 63) (degrees); dtheta = 30 exp(
+ *   -((hbar' - 275) / 25)^2); R_C = 2 sqrt(Cbar'^7 / (Cbar'^7 + 25^7)); S_L = 1 + 0.015 (Lbar' - 50)^2 / sqrt(20 + (Lbar' - 50)^2);
+ *   S_C = 1 + 0.045 Cbar'; S_H = 1 + 0.015 Cbar' T; R_T = -sin(2 dtheta) R_C; dE00 = sqrt(x^2 + y^2 + z^2 + R_T y z), x = dL' /
+ *   S_L, y = dC' / S_C, z = dH' / S_H.  No fused multiply-add: two identical pixels give exactly 0.0.
+ * u8: restored, gt planar uint8 (B,3,h,w), any h, w >= 1.  lin_table: 256 doubles on the device, the linear value of every
+ *   level by the formula above, built by the host in fp64 (hvi-cidnet_amd/metrics.py: ciede2000_tables): no pow runs on the
+ *   device for a level.  scale NULL: both sides are levels.  scale = B doubles on the device (GT mean; what
+ *   cidnet_metric_lpips_scale forms): the restored pixel enters as v = clip(q scale[b], 0, 255) / 255, a real number that is not
+ *   re-quantized (measure.py:138-141), through an fp64 pow; the ground truth still reads the table.  An image whose gray mean is
+ *   0 has an infinite or NaN scale and gives whatever IEEE arithmetic gives.  map (B,h,w doubles) receives every pixel's dE00,
+ *   mean (B doubles) the image values; either may be NULL, not both.  ws: cidnet_metric_ciede2000_ws_bytes(B, h, w) bytes,
+ *   read and written only with mean.
+ *   Reduction, no atomics: block x of an image takes pixels 1024 x .. 1024 x + 1023 of the flattened plane, thread t of its 256
+ *   the pixels 1024 x + 4 t + 0..3, added in that order onto 0.0; the block tree -- in each wave of 64 the butterfly v +=
+ *   v[lane ^ 32], ^ 16, ^ 8, ^ 4, ^ 2, ^ 1, then ((wave 0 + wave 1) + wave 2) + wave 3 -- gives slot x of the image in ws.  One
+ *   block per image then adds slots t, t + 256, ... in that order onto 0.0 in thread t, sums the threads by the same tree and
+ *   divides by h w.  The pixel -> block map depends on (h, w) only: bit-identical from call to call, and an image's value does
+ *   not depend on the rest of the batch.
+ *   restored / gt / lin_table NULL, map and mean both NULL, mean without ws, a pointer to doubles that is not 8-byte aligned, or
+ *   B, h or w < 1 is CIDNET_ERR_ARG; a short workspace CIDNET_ERR_WS; h w > 2^31 - 1 or B > 65535 CIDNET_ERR_SHAPE.
+ * ws_bytes: host only; 0 for sizes the launcher rejects.
+ * plan: host only, launches nothing; the function the launcher itself calls.  Writes out[0..2] = blocks per image, pixels per
+ *   block (blocks x pixels >= h w), static LDS bytes per block.  out NULL or n < 3 is CIDNET_ERR_ARG and nothing is written;
+ *   never writes past out[2]; the size errors are those above.
+ * lab: out[i] = dE00(lab1[i], lab2[i]) for n pairs of (L, a, b) doubles, (n,3) contiguous: the same core, so that it can be held
+ *   against published Lab data.  A NULL or misaligned pointer or n < 1 is CIDNET_ERR_ARG. */
+long cidnet_metric_ciede2000_ws_bytes(int B, int h, int w);
+int cidnet_metric_ciede2000_plan(int h, int w, int* out, int n);
+int cidnet_metric_ciede2000_u8(const uint8_t* restored, const uint8_t* gt, const double* scale, const double* lin_table, double* map,
+                               double* mean, void* ws, long ws_bytes, int B, int h, int w, void* stream);
+int cidnet_metric_ciede2000_lab(const double* lab1, const double* lab2, double* out, long n, void* stream);
 
 #ifdef __cplusplus
 }
