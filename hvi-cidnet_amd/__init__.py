@@ -23,12 +23,12 @@ from . import data
 from .data import ResidentPairs, TrainBatches, epoch_plan, scene_epoch_plan, scene_pairs, crop_flip, arena_layout, gamma_table
 from . import image_io
 from .image_io import ingest, egress, enhance_u8, enhance_folder, EnhanceReport, tile_plan, TilePlan, ingest_tiles, egress_tiles, png_plan, PngPlan, png_zlib_u8, png_file, png_encode_u8, jpeg_encode_plan, JpegEncodePlan, jpeg_scan_u8, jpeg_file, jpeg_encode_u8
-from .dp import StepLog
-from .fit import fit, run_epoch, epoch_stats
+from .dp import StepLog, TensorLog, tensor_stats_plan
+from .fit import fit, run_epoch, epoch_stats, diagnose_epoch, write_preview
 from .ops import set_storage_dtype, set_precision, set_math_levels
 
 __all__ = ["CIDNet", "CIDNet_MSSA", "SpatialAttention", "CIDNet_TNSM", "HV_TNSM", "I_TNSM", "TrainableNoiseSuppression", "RGB_HVI", "CAB", "IEL", "HV_LCA", "I_LCA", "LayerNorm", "NormDownsample", "NormUpsample", "L1Loss", "SSIM", "EdgeLoss", "CIDNetLoss", "tnsm_noise_loss", "PerceptualLoss", "VGGFeatureExtractor", "enhance", "load_weights", "save_pretrained", "pad_to_multiple",
            "WarmupCosineLR", "set_storage_dtype", "set_precision", "set_math_levels", "metrics", "evaluate", "folder_pairs", "nested_folder_pairs", "group_means", "evaluate_unpaired", "folder_images", "NiqeParams",
            "load_niqe_params", "loe", "loe_counts", "loe_grid", "jpeg_quant_plan", "jpeg_roundtrip_u8", "LpipsParams", "load_lpips_params", "lpips", "lpips_layers", "lpips_features", "lpips_feature_sizes", "ciede2000", "ciede2000_map", "ciede2000_lab", "ciede2000_tables", "data", "ResidentPairs", "TrainBatches", "epoch_plan", "scene_epoch_plan", "scene_pairs", "crop_flip", "arena_layout", "gamma_table",
-           "fit", "run_epoch", "epoch_stats", "StepLog", "image_io", "ingest", "egress", "enhance_u8", "enhance_folder", "EnhanceReport", "tile_plan", "TilePlan", "png_plan", "PngPlan", "png_zlib_u8", "png_file", "png_encode_u8", "jpeg_encode_plan", "JpegEncodePlan", "jpeg_scan_u8", "jpeg_file", "jpeg_encode_u8",
+           "fit", "run_epoch", "epoch_stats", "StepLog", "TensorLog", "tensor_stats_plan", "diagnose_epoch", "write_preview", "image_io", "ingest", "egress", "enhance_u8", "enhance_folder", "EnhanceReport", "tile_plan", "TilePlan", "png_plan", "PngPlan", "png_zlib_u8", "png_file", "png_encode_u8", "jpeg_encode_plan", "JpegEncodePlan", "jpeg_scan_u8", "jpeg_file", "jpeg_encode_u8",
            "ingest_tiles", "egress_tiles"]

@@ -236,6 +236,75 @@ class StepLog:
         return rows
 
 
+def tensor_stats_plan(offsets, lengths, n, device, kernel: Optional[bool] = None):
+    """-> the plan ops.tensor_stats takes for the segments (offsets[t], lengths[t]) of a flat fp32 buffer of n elements on
+    `device`: tile table and segment arrays uploaded once, workspace owned.  kernel None: the HIP kernel on a GPU, the
+    plain-torch restatement on the CPU; False: the restatement everywhere."""
+    from . import ops
+    return ops.TensorStatsPlan(offsets, lengths, n, device, kernel)
+
+
+class TensorLog:
+    """Beside StepLog: a (capacity, len(what), T, 4) fp64 device ring of per-tensor statistics (ops.tensor_stats: norm, maxabs,
+    nonfinite, first), one row per update, written on the stream of the update immediately before the guard.  what: "grad"
+    (the gradient the guard sees, with the guard's scale) and / or "weight" (the weights that produced it, scale 1).  T and
+    `names` -- the live parameters in arena order -- are only known when the trainer builds its arena, which binds the
+    log.  Update i since the last reset() writes row i % capacity; the index is a host integer, the same as the StepLog
+    row's.  read() is the only transfer: one device-to-host copy."""
+    NORM, MAXABS, NONFINITE, FIRST = 0, 1, 2, 3
+    WHAT = ("grad", "weight")
+
+    def __init__(self, capacity: int, what=("grad", "weight")):
+        self.capacity = int(capacity)
+        if self.capacity <= 0:
+            raise ValueError("TensorLog: capacity must be positive")
+        self.what = tuple(what)
+        if not self.what or len(set(self.what)) != len(self.what) or any(w not in self.WHAT for w in self.what):
+            raise ValueError(f"TensorLog: what must be a non-empty choice of {self.WHAT} (got {what!r})")
+        self.buf = None
+        self.names = None
+        self.issued = 0
+
+    def bind(self, device, names):
+        """allocate the ring on `device` for the tensors `names` (the trainer does this when it builds its arena)"""
+        names = tuple(names)
+        if self.buf is None or self.buf.device != torch.device(device) or names != self.names:
+            self.buf = torch.zeros((self.capacity, len(self.what), len(names), 4), dtype=torch.float64, device=device)
+            self.names = names
+        return self
+
+    def reset(self):
+        self.issued = 0
+
+    def next_row(self):
+        """-> the (len(what), T, 4) tensor of the update that is issued now"""
+        row = self.buf[self.issued % self.capacity]
+        self.issued += 1
+        return row
+
+    def read(self):
+        """rows written since reset() (the last `capacity` of them when more were issued), in step order, as a numpy array
+        (rows, len(what), T, 4)"""
+        import numpy as np
+        n = min(self.issued, self.capacity)
+        if n == 0 or self.buf is None:
+            return np.zeros((0, len(self.what), len(self.names or ()), 4), dtype=np.float64)
+        rows = self.buf[:n].cpu().numpy()
+        if self.issued > self.capacity:
+            rows = np.roll(rows, -(self.issued % self.capacity), axis=0)
+        return rows
+
+    def first_nonfinite(self, row, what="grad"):
+        """row: one row of read(), (len(what), T, 4).  -> (tensor index, name, element index) of the first tensor in arena
+        order that holds a non-finite element, or None.  Arena order is gradient-ready order: for "grad" this is the
+        parameter nearest the loss among the affected ones (DESIGN 6.16 for what that does and does not prove)."""
+        stats = row[self.what.index(what)]
+        for t in range(stats.shape[0]):
+            if stats[t, self.NONFINITE] > 0:
+                return t, self.names[t], int(stats[t, self.FIRST])
+        return None
+
+
 def rank_cpu_set(cpus, local_rank: int, local_world: int):
     """The contiguous share of `cpus` (sorted ids) that local rank `local_rank` of `local_world` ranks on this node gets:
     equal chunks, the remainder to the first ranks; every rank at least one CPU (ranks then share when CPUs are fewer)."""
@@ -274,7 +343,7 @@ class DataParallelTrainer:
                  max_steps_in_flight: int = 3, max_queued_bytes: Optional[int] = None,
                  prepared_weights: Optional[bool] = None, max_grad_norm: Optional[float] = None,
                  skip_nonfinite: bool = False, step_log: Optional[StepLog] = None, accum_steps: int = 1,
-                 ema_decay: Optional[float] = None):
+                 ema_decay: Optional[float] = None, tensor_log: Optional["TensorLog"] = None):
         """max_grad_norm / skip_nonfinite / step_log: the guarded step (FlatAdam's device-state path).  The guard runs after
         the all-reduce, where every rank holds the same gradient, so every rank takes the same decision without talking;
         step_log (a StepLog) receives one row per step.
@@ -286,8 +355,13 @@ class DataParallelTrainer:
         passes' losses in pass order, times fp32(1 / K)); pending_passes, flush().
         ema_decay: an exponential moving average of the weights, updated on the device behind every Adam launch and left
         alone by a step the guard skips (FlatAdam); ema_state_dict(), ema_weights().
-        With the defaults neither adds a launch, a value or a state_dict key."""
+        tensor_log (a TensorLog): per-tensor statistics of every update's gradient (the buffer and the scale the guard gets,
+        after the all-reduce, so every rank logs the same rows) and / or of the weights that produced it, launched on the
+        update's stream immediately before the guard (unguarded: before Adam); one row per update, the StepLog row's index.
+        With the defaults none of the three adds a launch, a value or a state_dict key."""
         self.model = model
+        self.tensor_log = tensor_log
+        self._stats_plan = None
         self.accum_steps = int(accum_steps)
         if self.accum_steps < 1:
             raise ValueError("accum_steps must be at least 1")
@@ -445,6 +519,10 @@ class DataParallelTrainer:
             self._loss_mean = torch.zeros(1, device=dev, dtype=torch.float32)    # what the guard logs for the update
         if self.step_log is not None:
             self.step_log.bind(dev)
+        if self.tensor_log is not None:
+            named = self._live_named()
+            self._stats_plan = tensor_stats_plan([r[1] for r in named], [r[2] for r in named], n_live, dev, kernel=self.use_hip)
+            self.tensor_log.bind(dev, [r[0] for r in named])
         self._ready = True
         if self._pending_state is not None:
             state, self._pending_state = self._pending_state, None
@@ -692,6 +770,8 @@ class DataParallelTrainer:
         flat_g / passes: the buffer that holds the summed gradient of an accumulated update and how many passes it sums."""
         flat_g = self.flat_g if flat_g is None else flat_g
         scale = 1.0 / (self.world * passes)
+        if self.tensor_log is not None:
+            self._log_tensors(flat_g, scale)
         if not self.opt.guarded:
             self.opt.step(flat_g, self.n_live, grad_scale=scale)
             return
@@ -699,6 +779,16 @@ class DataParallelTrainer:
         if row is not None and self.opt.kernel:
             row = row.data_ptr()
         self.opt.step(flat_g, self.n_live, grad_scale=scale, loss=loss.detach(), log_row=row)
+
+    def _log_tensors(self, flat_g, scale):
+        """the update's row of the tensor log: two launches per entry of its `what`, on the current stream"""
+        from . import ops
+        row, n = self.tensor_log.next_row(), self.n_live
+        for i, what in enumerate(self.tensor_log.what):
+            if what == "grad":
+                ops.tensor_stats(flat_g[:n], self._stats_plan, scale, out=row[i])
+            else:
+                ops.tensor_stats(self.flat_p[:n], self._stats_plan, 1.0, out=row[i])
 
     # ---- gradient accumulation --------------------------------------------------------------------------
     @property

@@ -19,8 +19,12 @@ What differs from the reference's loop:
     a NaN or an Inf is skipped on the device (skip_nonfinite) instead of poisoning the weights and both Adam moments;
   * `resume=` continues a run exactly (Adam moments, step counts, schedule position); the reference's own resume
     (`start_epoch` > 0: weights only, fresh Adam, restarted warm-up, shortened cosine period) is kept as it is;
-  * left out: the per-epoch training/test.png dump of the step's own output (the validation's enhanced images can be written:
-    val_args=dict(save_dir=...), metrics.evaluate), the metrics .md table (on_epoch hands the numbers to the caller), the
+  * the reference's two tools against gradient explosion are opt-in and device-side: diagnose=True logs per-tensor gradient
+    and weight statistics of every update (dp.TensorLog; what --grad_detect's set_detect_anomaly answers, without a host
+    wait or a second backward) and preview_dir= writes the per-epoch test.png / gt.png of train.py:84-89, clamped where
+    the reference's ToPILImage wraps (the validation's enhanced images can be written as well: val_args=dict(save_dir=...),
+    metrics.evaluate);
+  * left out: the metrics .md table (on_epoch hands the numbers to the caller), the
     option parser, the cyclic scheduler variant.  LPIPS is opt-in: val_args=dict(lpips=params or the two paths) adds
     `lpips` (and `lpips_ema`) to the record (metrics.evaluate(lpips=)); so is the CIEDE2000 colour difference:
     val_args=dict(ciede2000=True) adds `ciede2000` (and `ciede2000_ema`).
@@ -37,19 +41,23 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .dp import DataParallelTrainer, StepLog
+from .dp import DataParallelTrainer, StepLog, TensorLog
 from .schedule import WarmupCosineLR
 
 _SCHEDULE_KEYS = ("nEpochs", "lr", "warmup_epochs", "start_warmup", "start_epoch")
 
 
-def run_epoch(trainer, batches, epoch, step_log):
+def run_epoch(trainer, batches, epoch, step_log, last_batch=None):
     """The steps of one epoch and ONE read of the step log -> its rows, (updates, 4) fp64 (dp.StepLog's columns).  With
     accum_steps = K > 1 a batch is one pass and a row one update; a group the epoch's last batch leaves open is applied
-    from the passes it has (trainer.flush), so 61 batches with K = 4 are 16 updates, the last from one pass."""
+    from the passes it has (trainer.flush), so 61 batches with K = 4 are 16 updates, the last from one pass.
+    last_batch: a list that is cleared and then holds the epoch's last batch (fit's preview reads it)."""
     step_log.reset()
+    batch = None
     for batch in batches.epoch(epoch):                           # (x, gt) or (x, gt, raw): the third is the step's raw_input
         trainer.step(*batch)
+    if last_batch is not None:
+        last_batch[:] = [] if batch is None else [batch]
     if trainer.pending_passes > 0:
         trainer.flush()
     return step_log.read()
@@ -70,6 +78,62 @@ def epoch_stats(rows):
             "clipped": int((rows[applied, StepLog.COEF] < 1.0).sum())}
 
 
+def diagnose_epoch(rows, stats, names, what=("grad", "weight"), top=5):
+    """The record's `diagnosis` from an epoch's step log rows and tensor log rows (dp.TensorLog.read(): (updates, len(what),
+    T, 4)); names: the tensors in arena order.
+      nonfinite: one entry per update whose gradient held a non-finite element -- update (index in the epoch), applied,
+        tensors (the affected names in arena order) and origin (name, tensor, element of the first of them: the
+        parameter nearest the loss in gradient-ready order);
+      grad_top: the `top` tensors by their largest gradient norm over the applied updates -- name, norm, update;
+      weights_nonfinite: names of the tensors whose weights held a non-finite element at any update."""
+    n = min(rows.shape[0], stats.shape[0])
+    out = {"nonfinite": [], "grad_top": [], "weights_nonfinite": []}
+    applied = rows[:n, StepLog.COUNT] > 0
+    if "grad" in what:
+        g = stats[:n, what.index("grad")]
+        for u in range(n):
+            bad = np.flatnonzero(g[u, :, TensorLog.NONFINITE] > 0)
+            if bad.size:
+                t = int(bad[0])
+                out["nonfinite"].append({"update": u, "applied": bool(applied[u]), "tensors": [names[i] for i in bad],
+                                         "origin": {"name": names[t], "tensor": t, "element": int(g[u, t, TensorLog.FIRST])}})
+        if applied.any():
+            norms = np.where(applied[:, None], g[:, :, TensorLog.NORM], -1.0)
+            at = norms.argmax(axis=0)
+            best = norms[at, np.arange(norms.shape[1])]
+            order = sorted(range(len(names)), key=lambda i: (-best[i], i))[:max(int(top), 0)]
+            out["grad_top"] = [{"name": names[i], "norm": float(best[i]), "update": int(at[i])} for i in order]
+    if "weight" in what:
+        w = stats[:n, what.index("weight")]
+        out["weights_nonfinite"] = [names[i] for i in np.flatnonzero((w[:, :, TensorLog.NONFINITE] > 0).any(axis=0))]
+    return out
+
+
+def preview_bytes(img):
+    """(3, h, w) fp32 -> (h, w, 3) uint8 as a numpy array, trunc(clamp(v, 0, 1) * 255): image_io.egress on the device, its
+    plain-torch restatement for a CPU tensor"""
+    if img.is_cuda:
+        from . import image_io
+        return image_io.egress(img.unsqueeze(0).contiguous())[0].cpu().numpy()
+    return (img.detach().float().clamp(0, 1) * 255).to(torch.uint8).permute(1, 2, 0).contiguous().numpy()
+
+
+def write_preview(model, batch, preview_dir):
+    """The reference's per-epoch preview (train.py:84-89): test.png = the model's output for the first sample of `batch`
+    (a no_grad forward in the mode the model is in; a tuple result's first element), gt.png = that sample's ground truth,
+    each epoch over the last.  The reference hands the unclamped tensor to ToPILImage, whose .byte() wraps values outside
+    [0, 1]; this clamps."""
+    from PIL import Image
+    x, gt = batch[0], batch[1]
+    with torch.no_grad():
+        out = model(x[:1])
+    if isinstance(out, (tuple, list)):
+        out = out[0]
+    os.makedirs(preview_dir, exist_ok=True)
+    Image.fromarray(preview_bytes(out[0])).save(os.path.join(preview_dir, "test.png"))
+    Image.fromarray(preview_bytes(gt[0])).save(os.path.join(preview_dir, "gt.png"))
+
+
 def _model_device(model):
     for p in model.parameters():
         return p.device
@@ -78,7 +142,8 @@ def _model_device(model):
 
 def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, start_epoch=0, snapshots=10, loss_fn=None,
         max_grad_norm=None, skip_nonfinite=True, val_pairs=None, val_args=None, out_dir=None, resume=None,
-        process_group=None, on_epoch=None, trainer_args=None, accum_steps=1, ema_decay=None, val_weights="model"):
+        process_group=None, on_epoch=None, trainer_args=None, accum_steps=1, ema_decay=None, val_weights="model",
+        diagnose=False, diagnose_top=5, preview_dir=None):
     """Train `model` for the epochs start_epoch + 1 ... start_epoch + nEpochs and return one record per epoch.
 
     batches: anything with __len__ (steps per epoch) and epoch(e) yielding (x, gt) or (x, gt, raw): data.TrainBatches.
@@ -103,7 +168,14 @@ def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, star
     ema_decay: the trainer keeps an exponential moving average of the weights; a snapshot also writes epoch_{epoch}.ema.pth
     (trainer.ema_state_dict(), the same checkpoint format) and `resume=` restores the average with the rest.
     val_weights: "model" validates the trained weights (psnr / ssim), "ema" the averaged ones (psnr_ema / ssim_ema,
-    evaluated inside trainer.ema_weights()), "both" both; "ema" and "both" need ema_decay."""
+    evaluated inside trainer.ema_weights()), "both" both; "ema" and "both" need ema_decay.
+    diagnose: the trainer also writes a dp.TensorLog sized like the step log (per-tensor statistics of every update's
+    gradient and weights, four more launches per update and nothing else), read once per epoch beside the step log; the
+    record gains `diagnosis` (diagnose_epoch: nonfinite, grad_top with diagnose_top entries, weights_nonfinite).  Nothing of
+    it is stored in a snapshot.
+    preview_dir: after every epoch rank 0 writes test.png and gt.png there (write_preview) from the first sample of the
+    epoch's last batch, after the epoch's last update.
+    With the defaults neither adds a launch or a record key."""
     if val_weights not in ("model", "ema", "both"):
         raise ValueError(f"fit: val_weights must be 'model', 'ema' or 'both' (got {val_weights!r})")
     if val_weights != "model" and ema_decay is None:
@@ -121,9 +193,13 @@ def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, star
     if len(batches) <= 0:
         raise ValueError("fit: an epoch without steps")
     log = StepLog(-(-len(batches) // accum_steps))                # one row per update
+    extra = dict(trainer_args or {})
+    tlog = None
+    if diagnose:
+        tlog = extra["tensor_log"] = TensorLog(log.capacity)
     trainer = DataParallelTrainer(model, lr=sched.lr_after(0), loss_fn=loss_fn, process_group=process_group,
                                   max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, step_log=log,
-                                  accum_steps=accum_steps, ema_decay=ema_decay, **(trainer_args or {}))
+                                  accum_steps=accum_steps, ema_decay=ema_decay, **extra)
     first, done = sched_args["start_epoch"] + 1, 0
     if resume is not None:
         saved = torch.load(resume, map_location="cpu", weights_only=False)
@@ -141,9 +217,16 @@ def fit(model, batches, *, nEpochs, lr, warmup_epochs=3, start_warmup=True, star
     for epoch in range(first, sched_args["start_epoch"] + sched_args["nEpochs"] + 1):
         lr_now = sched.apply(trainer, done)
         model.train()
-        rows = run_epoch(trainer, batches, epoch, log)
+        last = [] if preview_dir is not None else None
+        if tlog is not None:
+            tlog.reset()
+        rows = run_epoch(trainer, batches, epoch, log, last_batch=last)
         done += 1
         rec = {"epoch": epoch, "lr": lr_now, **epoch_stats(rows)}
+        if tlog is not None:
+            rec["diagnosis"] = diagnose_epoch(rows, tlog.read(), tlog.names, tlog.what, diagnose_top)
+        if last and rank == 0:
+            write_preview(model, last[0], preview_dir)
         if world > 1:
             t = torch.tensor([rec["loss"]], dtype=torch.float64, device=_model_device(model))
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)

@@ -1529,6 +1529,89 @@ def swap(a, b):
     lib().call("cidnet_swap", _p(a), _p(b), a.numel(), _stream())
 
 
+STATS_NORM, STATS_MAXABS, STATS_NONFINITE, STATS_FIRST = 0, 1, 2, 3      # include/cidnet_hip.h: cidnet_tensor_stats
+STATS_COLS, STATS_TILE = 4, 4096
+
+
+class TensorStatsPlan:
+    """The layout one tensor_stats() call works on: T segments (offsets[t], lengths[t]) of a flat fp32 buffer of n elements.
+    kernel (default: the device is a GPU): the library's plan query (cidnet_tensor_stats_plan, host only) checks the segments
+    and fills the tile table; table and segment arrays are uploaded here, once, and the workspace is owned, so a call copies
+    and allocates nothing.  kernel=False, or a CPU device: tensor_stats() runs the plain-torch restatement and the plan
+    only checks and keeps the segments.  dp.tensor_stats_plan builds one."""
+
+    def __init__(self, offsets, lengths, n, device, kernel=None):
+        self.offsets, self.lengths = [int(o) for o in offsets], [int(c) for c in lengths]
+        self.T, self.n, self.device = len(self.offsets), int(n), torch.device(device)
+        if len(self.lengths) != self.T:
+            raise ValueError("tensor_stats_plan: offsets and lengths differ in length")
+        self.kernel = self.device.type == "cuda" if kernel is None else bool(kernel)
+        if self.kernel and self.device.type != "cuda":
+            raise RuntimeError("tensor_stats_plan: the kernel runs on a ROCm device only (kernel=False restates it in torch)")
+        if not self.kernel:
+            if self.T < 1 or self.n < 1 or any(c < 1 or o < 0 or o + c > self.n for o, c in zip(self.offsets, self.lengths)):
+                raise RuntimeError("tensor_stats_plan: every segment must be non-empty and lie inside the buffer")
+            self.seg_tiles = [-(-c // STATS_TILE) for c in self.lengths]
+            self.tiles = sum(self.seg_tiles)
+            return
+        self._off = (ctypes.c_long * max(self.T, 1))(*self.offsets)
+        self._len = (ctypes.c_long * max(self.T, 1))(*self.lengths)
+        sizes = (ctypes.c_long * 3)()
+        lib().call("cidnet_tensor_stats_plan", self._off, self._len, self.T, self.n, sizes, 3, None, None, 0)
+        self.tiles, self.ws_bytes, table_ints = int(sizes[0]), int(sizes[1]), int(sizes[2])
+        seg, table = (ctypes.c_int * self.T)(), (ctypes.c_int * table_ints)()
+        lib().call("cidnet_tensor_stats_plan", self._off, self._len, self.T, self.n, sizes, 3, seg, table, table_ints)
+        self.seg_tiles, self.table = list(seg), list(table)
+        self.off_dev = torch.tensor(self.offsets, dtype=torch.int64, device=self.device)
+        self.len_dev = torch.tensor(self.lengths, dtype=torch.int64, device=self.device)
+        self.table_dev = torch.tensor(self.table, dtype=torch.int32, device=self.device)
+        self.ws = torch.empty(self.ws_bytes // 8, dtype=torch.float64, device=self.device)
+
+
+def tensor_stats_torch(buf, offsets, lengths, scale=1.0, out=None):
+    """Plain-torch restatement of cidnet_tensor_stats (the CPU / gloo tests of the trainer; also runs on a device tensor): row t
+    = norm and largest magnitude of the finite elements of buf[off:off + len] times (double) fp32(scale), the number of
+    non-finite elements, the index of the first (-1: none)."""
+    s = float(ctypes.c_float(float(scale)).value)
+    if not (0.0 <= s < float("inf")):
+        raise RuntimeError("tensor_stats: the scale must be finite and not negative")
+    rows = []
+    for o, c in zip(offsets, lengths):
+        x = buf[o:o + c]
+        bad = ~torch.isfinite(x)
+        xf = torch.where(bad, torch.zeros_like(x), x)
+        cnt = bad.sum()
+        first = torch.where(cnt > 0, bad.to(torch.uint8).argmax(), torch.full_like(cnt, -1))
+        rows.append(torch.stack([xf.double().pow(2).sum().sqrt() * s, xf.abs().max().double() * s, cnt.double(), first.double()]))
+    res = torch.stack(rows)
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
+def tensor_stats(buf, plan, scale=1.0, out=None):
+    """cidnet_tensor_stats on the current stream -> (T, 4) fp64 on buf's device: per segment of `plan` the norm and the largest
+    magnitude of the finite elements, both times fp32(scale), the number of non-finite elements and the index of the first
+    (-1: none).  buf: the contiguous fp32 buffer of plan.n elements the plan was made for.  A negative, NaN or infinite
+    scale is refused.  Two launches, no copy, no allocation when `out` is given.  On a CPU buffer, or with a kernel=False
+    plan, the plain-torch restatement runs instead."""
+    if buf.dtype != torch.float32 or buf.dim() != 1 or not buf.is_contiguous() or buf.numel() != plan.n:
+        raise RuntimeError(f"tensor_stats: one contiguous fp32 buffer of {plan.n} elements")
+    if out is not None and not (out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (plan.T, STATS_COLS)
+                                and out.device == buf.device):
+        raise RuntimeError(f"tensor_stats: out must be a contiguous ({plan.T}, {STATS_COLS}) fp64 tensor on the buffer's device")
+    if not plan.kernel or not buf.is_cuda:
+        return tensor_stats_torch(buf, plan.offsets, plan.lengths, scale, out)
+    if buf.device != plan.device:
+        raise RuntimeError("tensor_stats: the plan was uploaded to another device")
+    if out is None:
+        out = torch.empty((plan.T, STATS_COLS), dtype=torch.float64, device=buf.device)
+    lib().call("cidnet_tensor_stats", _p(buf), plan.n, plan._off, plan._len, plan.T, _p(plan.off_dev), _p(plan.len_dev),
+               _p(plan.table_dev), _f(scale), _p(out), _p(plan.ws), plan.ws_bytes, _stream())
+    return out
+
+
 # --------------------------------------------------------------------------------------------
 # gradient arena: weight gradients are written straight into one flat buffer (the all-reduce /
 # optimizer operand) instead of 191 separately allocated tensors.  The op layer reads the active

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 24
+#define CIDNET_ABI_VERSION 25
 
 int cidnet_abi_version(void);
 
@@ -494,6 +494,43 @@ int cidnet_adam_step_dev(float* p, const float* g, float* m, float* v, long n, f
 int cidnet_grad_accumulate(float* dst, const float* src, long n, int first, void* stream);
 int cidnet_ema_update(float* ema, const float* p, long n, float w, const float* record, void* stream);
 int cidnet_swap(float* a, float* b, long n, void* stream);
+/* Per-tensor statistics of a flat fp32 buffer (csrc/tensor_stats.hip): which slice of the trainer's gradient / weight arena
+ * went non-finite, and which one carries the norm.  The reference's tools for this are host-side (--grad_detect:
+ * torch.autograd.set_detect_anomaly, train.py:47; the per-epoch preview image, train.py:84-89); the contract is this text.
+ * buf[0..n) and T segments (off[t], len[t]), in ELEMENTS: any order, adjacent or not, overlapping or not, aligned to 4 bytes
+ * only.  Nothing outside a segment is read.  With x_i = buf[off[t] + i] and s = scale, row t of out (T x 4 doubles) is
+ *   [0] norm      = sqrt(sum of (double) x_i^2 over the FINITE x_i) * (double) s   (one NaN does not erase the rest)
+ *   [1] maxabs    = max of |x_i| over the finite x_i (0 when none is finite) * (double) s
+ *   [2] nonfinite = how many x_i are NaN or +-Inf, exact
+ *   [3] first     = the smallest i with a non-finite x_i, -1 when there is none
+ * An element is classified by its exponent bits first and then either added or counted; no fmax carries a NaN.
+ * Tiles: segment t is cut into ceil(len[t] / 4096) tiles of 4096 elements (the last one shorter); the tiles of all segments,
+ * segment after segment, are numbered 0 .. tiles - 1.  table (T + 2 tiles int32): table[t] = the number of segment t's
+ * first tile; table[T + 2 j], table[T + 2 j + 1] = segment and index inside the segment of tile j.
+ * Launch 1, one block of 256 threads per tile: thread h reads elements 1024 q + 4 h + 0..3 of the tile for q = 0..3 (one
+ *   unaligned 16-byte load where all four are inside the tile, scalar loads for the tile's last 1..3), adds the squares in
+ *   that order onto 0.0 in fp64 (the square of an fp32 value is exact there); in each wave of 64 the butterfly v += v[lane ^
+ *   32], ^ 16, ^ 8, ^ 4, ^ 2, ^ 1, then ((wave 0 + wave 1) + wave 2) + wave 3 -> slot j of ws (32 bytes: sum, max, count, first).
+ * Launch 2, one wave per segment: lane l adds the segment's slots l, l + 64, ... in that order onto 0.0, the same butterfly,
+ *   and lane 0 writes the row.
+ * No atomics, no hand-off between blocks inside a launch: bit-identical from call to call, and a segment's row does not depend
+ * on which other segments the call has.
+ * plan: host only, launches nothing; the function the launcher itself calls.  off, len: T host values.  Writes out[0..2] =
+ *   tiles, workspace bytes (32 tiles), table length in int32 (T + 2 tiles); seg_tiles (T int32, may be NULL) = tiles per
+ *   segment; table (may be NULL: sizes only) = the table above, table_ints its capacity.  off / len / out NULL, n_out < 3,
+ *   T < 1, n < 1, a len < 1, an off < 0, off + len > n, or a table shorter than T + 2 tiles is CIDNET_ERR_ARG; T or tiles above
+ *   2^30 is CIDNET_ERR_SHAPE (the tile numbers are int32, with room for a grid).  On an error nothing is written; never writes
+ *   past out[2], seg_tiles[T - 1], table[T + 2 tiles - 1].
+ * The launcher takes the HOST off / len (checked as by plan on every call; the device is not asked) and their device copies
+ *   off_dev / len_dev (T int64 each), table_dev (the uploaded table), out (T x 4 doubles, device) and ws (32 tiles bytes,
+ *   8-byte aligned).  A NULL pointer, a misaligned out or ws, or a scale that is negative, NaN or infinite is CIDNET_ERR_ARG
+ *   (a norm has no sign to give; the trainer's 1 / (world passes) is positive), with plan's errors; a short workspace
+ *   CIDNET_ERR_WS.  What off_dev / len_dev / table_dev hold is the caller's word: THEY MUST BE THE COPIES OF WHAT WAS CHECKED. */
+int cidnet_tensor_stats_plan(const long* off, const long* len, long T, long n, long* out, int n_out, int* seg_tiles, int* table,
+                             long table_ints);
+int cidnet_tensor_stats(const float* buf, long n, const long* off, const long* len, long T, const long* off_dev,
+                        const long* len_dev, const int* table_dev, float scale, double* out, void* ws, long ws_bytes,
+                        void* stream);
 
 /* ---- K13: SpatialAttention of the MSSA variant (net/CIDNet_MSSA.py:10-25) ------------------------
  * out = x * sigmoid(conv7x7([mean_c x, max_c x])), w: (1,2,7,7).  stats (B,2,H,W), amax (B,H,W int32)

@@ -7,6 +7,9 @@ per measurement:
                  every step (the reference's way, train.py:75), alternated three times, over a synthetic resident set
   accum_ema      --accum K and / or --ema DECAY: ms per pass of the guarded step with accum_steps=K / ema_decay=DECAY against
                  the guarded step without them, alternated three times (nothing else is measured in such a run)
+  diagnose       --diagnose: ms per step of the guarded step with the per-tensor log (dp.TensorLog, gradient and weights: four
+                 more launches per update) against the guarded step without it, alternated three times (nothing else is
+                 measured in such a run); with --trace-run a few steps of both for a rocprofv3 run
   kernels        --share PATH: time per launch of the guard's kernels from the kernel_stats.csv of a run under
                  rocprofv3 --kernel-trace --stats (a run of its own: --trace-run launches only a few guarded steps)
 
@@ -14,6 +17,7 @@ Every line is printed and appended to --out (default profiles/fit_<precision>.js
 
     python tools/bench_fit.py [--precision f32|bf16] [--steps 20] [--pairs 64] [--out FILE]
     python tools/bench_fit.py [--precision f32|bf16] [--steps 20] --accum 4 --ema 0.999
+    python tools/bench_fit.py [--precision f32|bf16] [--steps 20] --diagnose
     rocprofv3 --kernel-trace --stats -f csv -d OUT -o run -- python tools/bench_fit.py --trace-run
     python tools/bench_fit.py --share OUT/.../run_kernel_stats.csv
 """
@@ -28,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 H, W, B = 400, 600, 8
-GUARD_KERNELS = ("sumsq_kernel", "guard_finish_kernel", "adam_dev_kernel", "adam_kernel")
+GUARD_KERNELS = ("sumsq_kernel", "guard_finish_kernel", "adam_dev_kernel", "adam_kernel", "stats_tile_kernel", "stats_finish_kernel")
 
 
 _OUT = None
@@ -69,6 +73,7 @@ def main():
     ap.add_argument("--share", default=None, help="kernel_stats.csv of a rocprofv3 run of this tool with --trace-run")
     ap.add_argument("--accum", type=int, default=1, help="K: time the guarded step with accum_steps=K against the plain one")
     ap.add_argument("--ema", type=float, default=None, help="DECAY: time the guarded step with ema_decay=DECAY against the plain one")
+    ap.add_argument("--diagnose", action="store_true", help="time the guarded step with a TensorLog against the plain one")
     ap.add_argument("--out", default=None, help="file the JSON lines are appended to")
     a = ap.parse_args()
     global _OUT
@@ -116,6 +121,27 @@ def main():
                 emit({"what": "accum_ema", "precision": a.precision, "mode": name, "accum": a.accum if name == "feature" else 1,
                       "ema": a.ema if name == "feature" else None, "rep": rep, "passes": passes,
                       "ms_per_pass": t / passes * 1e3})
+        return
+    if a.diagnose:
+        torch.manual_seed(0)
+        feat = DataParallelTrainer(P.CIDNet().to(dev), lr=1e-4, max_grad_norm=1.0, skip_nonfinite=True,
+                                   step_log=P.StepLog(64), tensor_log=P.TensorLog(64))
+        pair = {"plain": trainer(True), "diagnose": feat}
+        for tr in pair.values():
+            for _ in range(5):
+                tr.step(x0, gt0)
+        torch.cuda.synchronize()
+        for rep in range(1 if a.trace_run else 3):
+            for name, tr in pair.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    tr.step(x0, gt0)
+                torch.cuda.synchronize()
+                t = time.perf_counter() - t0
+                if not a.trace_run:
+                    emit({"what": "diagnose", "precision": a.precision, "mode": name, "rep": rep, "steps": a.steps,
+                          "ms_per_step": t / a.steps * 1e3})
         return
     trainers = {"guard_off": trainer(False), "guard_on": trainer(True)}
     for tr in trainers.values():
