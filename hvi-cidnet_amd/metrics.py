@@ -39,7 +39,15 @@ and the file round trip of the .jpg sets (eval.py saves such an output as a JPEG
     r = M.jpeg_roundtrip_u8(q, quality=75)          # uint8 (B,3,h,w) -> what PIL's save(.., 'JPEG') + open() returns, byte for byte
     res = M.evaluate_unpaired(model, images, prm, file_roundtrip=True)      # .jpg / .jpeg names scored as their decoded files
 
-The kernels are csrc/metrics.hip, csrc/lpips.hip, csrc/ciede2000.hip, csrc/resize.hip, csrc/niqe.hip, csrc/loe.hip and csrc/jpeg.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
+and BRISQUE, the second number of measure_niqe_bris.py (imquality.brisque.score), all fp64 on the device:
+
+    bp = M.load_brisque_params(model_path, range_path)    # libsvm text model + normalize.pickle / .npz (not shipped)
+    f = M.brisque_features(q)                       # uint8 (B,3,h,w), h, w >= 16 -> (B,36) fp64 on the device
+    s = M.brisque(q, bp)                            # (B,) fp64 on the device, no host synchronisation; M.brisque_score(f, bp)
+    y = M.brisque_gray(q); y2 = M.brisque_half(y); m, mom = M.brisque_mscn(y); f18 = M.brisque_fit(mom)      # the stages
+    res = M.evaluate_unpaired(model, images, prm, brisque=bp)       # res.brisque, res.per_image["brisque"]
+
+The kernels are csrc/metrics.hip, csrc/lpips.hip, csrc/ciede2000.hip, csrc/resize.hip, csrc/niqe.hip, csrc/brisque.hip, csrc/loe.hip and csrc/jpeg.hip (C ABI: cidnet_metric_*); their semantics are documented in include/cidnet_hip.h.
 Differences from the reference scripts, none of which changes a per-image value:
   * measure.py counts a low image without a ground truth in the divisor of its averages (it skips the image after
     `n += 1`); here such an image is skipped and reported (FolderPairs.skipped, EvalResult.skipped) and not counted;
@@ -55,7 +63,9 @@ Differences from the reference scripts, none of which changes a per-image value:
     dE00 between the output and the ground truth with scikit-image's sRGB -> Lab constants, in fp64;
   * NIQE: the half-size image sums its 8 taps in fp64 and rounds once per pass where the reference sums them in fp32 (two
     fp32 ulps apart at most), and the block moments are summed in fp64 where the reference's are fp32 means; an image with
-    fewer than two NaN-free blocks scores NaN (the reference raises from inside the SVD); BRISQUE is not computed; and by
+    fewer than two NaN-free blocks scores NaN (the reference raises from inside the SVD); BRISQUE, the script's second
+    number, is opt-in (brisque(), evaluate_unpaired(brisque=)): its model and range files are the user's own,
+    passed by path, and its stages are pinned to scipy / scikit-learn, not to the imquality package itself; and by
     default the score is that of the quantized output itself, while for a .jpg input eval.py's output file is a JPEG and the
     reference scores what that file decodes to: evaluate_unpaired(file_roundtrip=True) scores exactly that.
 """
@@ -1036,19 +1046,20 @@ def jpeg_roundtrip_u8(q: torch.Tensor, quality: int = 75) -> torch.Tensor:
 
 @dataclass
 class UnpairedResult:
-    """Mean NIQE -- and mean LOE, where evaluate_unpaired(loe=True) asked for it, else NaN -- over the evaluated images (running
-    sum in input order, divided by their number) and the per-image values"""
+    """Mean NIQE -- and mean LOE and mean BRISQUE, where evaluate_unpaired(loe=True) / (brisque=params) asked for them, else
+    NaN -- over the evaluated images (running sum in input order, divided by their number) and the per-image values"""
     alpha: float
     niqe: float
-    per_image: dict = field(default_factory=dict)     # "niqe" (and "loe") -> list, input order
+    per_image: dict = field(default_factory=dict)     # "niqe" (and "loe", "brisque") -> list, input order
     names: list = field(default_factory=list)
     ensemble: int = 1                                 # the number of views each output was averaged over
     loe: float = math.nan                             # mean lightness order error against the inputs as supplied
+    brisque: float = math.nan                         # mean BRISQUE score of the outputs
 
 
 def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batch_size: int = 1, process_group=None,
                       save_dir=None, ensemble: int = 1, loe: bool = False, loe_sample=50, file_roundtrip: bool = False,
-                      jpeg_quality: int = 75, png: str = "pillow", jpeg: str = "pillow"):
+                      jpeg_quality: int = 75, png: str = "pillow", jpeg: str = "pillow", brisque=None):
     """eval.py --unpaired + measure_niqe_bris.py on the device.  `images`: a sequence of (3,h,w) float images in [0, 1] (or
     uint8 HWC images, converted as ToTensor() does; folder_images() yields these), each at least 96 x 96.  Each is reflect-
     padded to a multiple of 8, run through model(pow(x, gamma)) in eval mode under no_grad with trans.gated2 = True and
@@ -1072,10 +1083,15 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
     and LOE, when asked for -- sees.  Other names and unnamed images are untouched, each image of a batch by its own name;
     per_image["file_roundtrip"] holds one bool per image.  save_dir still receives the un-round-tripped output: its .jpg,
     decoded again, is exactly what was scored.  False: nothing of it runs and the result is what it was without the keyword.
+    brisque: a BrisqueParams or the (libsvm model, range file) pair of paths -- each output is also scored with BRISQUE
+    (brisque(), measure_niqe_bris.py's second number) on the same bytes NIQE sees, after the file round trip where that applies.
+    UnpairedResult.brisque is the mean, per_image["brisque"] the values, after "niqe" and "loe".  None: nothing of it runs,
+    UnpairedResult.brisque is NaN and the result is what it was without the keyword.
     The model's attributes and the train / eval mode of every submodule are restored afterwards.
-    Not reproduced: BRISQUE (its place as the second unpaired number is taken by the opt-in LOE).  Without file_roundtrip=True
+    Without file_roundtrip=True
     the score is the quantized output's, not that of a lossy file decoded again (.jpg names: DICM, NPE, VV)."""
     prm = _niqe_params(params)
+    bprm = _brisque_params(brisque) if brisque is not None else None
     names = getattr(images, "names", None)
     if file_roundtrip:
         jpeg_quant_plan(jpeg_quality)                            # a bad quality raises before anything runs
@@ -1096,17 +1112,20 @@ def evaluate_unpaired(model, images, params, alpha=1.0, gamma: float = 1.0, batc
         elif flagged:                                            # a batch of mixed names: each image its own treatment
             q = q.clone()
             q[flagged] = jpeg_roundtrip_u8(q[flagged], jpeg_quality)
-        if not loe:
-            return (niqe(q, prm),)
-        low = torch.stack([a[0] for a in aux]) if len(aux) > 1 else aux[0][0].unsqueeze(0)
-        return niqe(q, prm), _loe_launch(low, q, loe_sample)[1]      # loe(): the keyword shadows its name in here
+        out = [niqe(q, prm)]
+        if loe:
+            low = torch.stack([a[0] for a in aux]) if len(aux) > 1 else aux[0][0].unsqueeze(0)
+            out.append(_loe_launch(low, q, loe_sample)[1])       # loe(): the keyword shadows its name in here
+        if bprm is not None:
+            out.append(brisque_score(brisque_features(q), bprm))  # brisque(): shadowed likewise
+        return tuple(out)
 
     def result(per_image, **kw):
         if file_roundtrip:
             per_image["file_roundtrip"] = list(lossy)
         return UnpairedResult(per_image=per_image, ensemble=int(ensemble), **kw)
     return _evaluate("evaluate_unpaired", "images", model, images, load, dict(gated2=True), score,
-                     ("niqe", "loe") if loe else ("niqe",), result, alpha,
+                     ("niqe",) + (("loe",) if loe else ()) + (("brisque",) if bprm is not None else ()), result, alpha,
                      gamma, batch_size, process_group, save_dir, ensemble=ensemble, png=png, jpeg=jpeg)
 
 
@@ -1442,3 +1461,281 @@ def ciede2000(restored_u8: torch.Tensor, gt_u8: torch.Tensor, gt_mean: bool = Fa
 def _ciede_both(q, g):
     """evaluate()'s CIEDE2000 columns of a checked batch: (plain, GT mean)"""
     return _ciede_launch(q, g, None, False, True)[1], _ciede_launch(q, g, _lpips_scale(q, g), False, True)[1]
+
+
+# ---- BRISQUE (measure_niqe_bris.py:26 -> imquality.brisque.score; csrc/brisque.hip, DESIGN.md 6.17) ---------------------------
+BRISQUE_MIN = 16
+BRISQUE_FEATURES = 36
+_BRISQUE_NO_PARAMS = ("BRISQUE needs the trained support-vector model and the feature ranges: pass a BrisqueParams or the pair of "
+                      "paths (libsvm text model, normalize.pickle or an .npz with min_ / max_; load_brisque_params); neither file "
+                      "is shipped with this package")
+
+
+@dataclass
+class BrisqueParams:
+    """The epsilon-SVR of BRISQUE (RBF kernel) and the feature ranges it was trained under: sv (n,36), coef (n,), rho, gamma,
+    fmin (36,), fmax (36,), fp64 host arrays.  on(device) uploads them once per device."""
+    sv: np.ndarray
+    coef: np.ndarray
+    rho: float
+    gamma: float
+    fmin: np.ndarray
+    fmax: np.ndarray
+    _dev: dict = field(default_factory=dict, repr=False, compare=False)      # device index -> (sv, coef, fmin, fmax, rho_gamma)
+
+    def __post_init__(self):
+        self.sv = np.ascontiguousarray(self.sv, dtype=np.float64)
+        self.coef = np.ascontiguousarray(self.coef, dtype=np.float64).reshape(-1)
+        self.fmin = np.ascontiguousarray(self.fmin, dtype=np.float64).reshape(-1)
+        self.fmax = np.ascontiguousarray(self.fmax, dtype=np.float64).reshape(-1)
+        self.rho, self.gamma = float(self.rho), float(self.gamma)
+        n = self.coef.size
+        if n < 1 or self.sv.shape != (n, BRISQUE_FEATURES) or self.fmin.size != BRISQUE_FEATURES or self.fmax.size != BRISQUE_FEATURES:
+            raise ValueError(f"BrisqueParams: expected sv (n,36), coef (n,), fmin (36,), fmax (36,); got {self.sv.shape}, "
+                             f"{self.coef.shape}, {self.fmin.shape}, {self.fmax.shape}")
+
+    def on(self, device):
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        if key not in self._dev:
+            rg = np.array([self.rho, self.gamma], dtype=np.float64)
+            self._dev[key] = tuple(torch.from_numpy(a).to(device) for a in (self.sv, self.coef, self.fmin, self.fmax, rg))
+        return self._dev[key]
+
+    @classmethod
+    def random(cls, seed: int = 0, n_sv: int = 64) -> "BrisqueParams":
+        """Stand-ins for tests only: scores from them mean nothing.  The ranges bracket what the features of noisy images take,
+        and rho keeps the score away from a cancellation to zero."""
+        rng = np.random.default_rng(seed)
+        fmin = -rng.uniform(0.1, 1.0, BRISQUE_FEATURES)
+        fmax = fmin + rng.uniform(2.0, 6.0, BRISQUE_FEATURES)
+        return cls(rng.uniform(-1.0, 1.0, (int(n_sv), BRISQUE_FEATURES)), rng.normal(0.0, 1.0, int(n_sv)),
+                   -(3.0 + rng.uniform()), 0.05, fmin, fmax)
+
+
+def _brisque_model(path):
+    """the libsvm text model of an epsilon-SVR with an RBF kernel -> (sv (n,36), coef (n,), rho, gamma)"""
+    with open(path) as f:
+        lines = [l.strip() for l in f.read().splitlines() if l.strip()]
+    head, at = {}, None
+    for i, l in enumerate(lines):
+        if l == "SV":
+            at = i + 1
+            break
+        parts = l.split()
+        # nr_class is written by libsvm for every model type (2 for a regression) and carries nothing here
+        if parts[0] not in ("svm_type", "kernel_type", "gamma", "total_sv", "rho", "nr_class") or len(parts) != 2:
+            raise ValueError(f"load_brisque_params: {path}: unexpected header line {l!r} (an epsilon_svr / rbf libsvm text model "
+                             "has svm_type, kernel_type, gamma, nr_class, total_sv, rho, then SV)")
+        head[parts[0]] = parts[1]
+    if at is None:
+        raise ValueError(f"load_brisque_params: {path}: no SV line (not a libsvm text model, or a truncated one)")
+    missing = [k for k in ("svm_type", "kernel_type", "gamma", "total_sv", "rho") if k not in head]
+    if missing:
+        raise ValueError(f"load_brisque_params: {path}: the header lacks {', '.join(missing)}")
+    if head["svm_type"] != "epsilon_svr" or head["kernel_type"] != "rbf":
+        raise ValueError(f"load_brisque_params: {path}: svm_type {head['svm_type']} / kernel_type {head['kernel_type']}; only "
+                         "epsilon_svr with an rbf kernel is BRISQUE's model")
+    try:
+        n, gamma, rho = int(head["total_sv"]), float(head["gamma"]), float(head["rho"])
+    except ValueError:
+        raise ValueError(f"load_brisque_params: {path}: gamma, total_sv or rho is not a number") from None
+    body = lines[at:]
+    if n < 1 or len(body) != n:
+        raise ValueError(f"load_brisque_params: {path}: total_sv says {n} support vectors, the file holds {len(body)}")
+    sv, coef = np.zeros((n, BRISQUE_FEATURES)), np.zeros(n)
+    for i, l in enumerate(body):
+        parts = l.split()
+        try:
+            coef[i] = float(parts[0])
+            for p in parts[1:]:
+                k, v = p.split(":")
+                k = int(k)
+                if not 1 <= k <= BRISQUE_FEATURES:
+                    raise IndexError(k)
+                sv[i, k - 1] = float(v)                          # an index that is absent stays 0
+        except IndexError as e:
+            raise ValueError(f"load_brisque_params: {path}: support vector {i} has feature index {e.args[0]}; BRISQUE has "
+                             f"{BRISQUE_FEATURES} features, numbered from 1") from None
+        except ValueError:
+            raise ValueError(f"load_brisque_params: {path}: support vector {i} is not `coef index:value ...`: {l[:60]!r}") from None
+    return sv, coef, rho, gamma
+
+
+def _brisque_range(path):
+    """min_ / max_ of the 36 features from imquality's normalize.pickle (a mapping, or an object with these attributes) or an
+    .npz with these keys"""
+    if str(path).lower().endswith(".npz"):
+        with np.load(path) as z:
+            missing = [k for k in ("min_", "max_") if k not in z.files]
+            if missing:
+                raise ValueError(f"load_brisque_params: {path} lacks {', '.join(missing)}")
+            lo, hi = np.array(z["min_"], dtype=np.float64), np.array(z["max_"], dtype=np.float64)
+    else:
+        import pickle
+        with open(path, "rb") as f:
+            obj = pickle.load(f)
+        try:
+            lo, hi = (obj["min_"], obj["max_"]) if isinstance(obj, dict) else (obj.min_, obj.max_)
+        except (KeyError, AttributeError):
+            raise ValueError(f"load_brisque_params: {path} holds neither min_ nor max_") from None
+        lo, hi = np.array(lo, dtype=np.float64), np.array(hi, dtype=np.float64)
+    if lo.size != BRISQUE_FEATURES or hi.size != BRISQUE_FEATURES:
+        raise ValueError(f"load_brisque_params: {path}: min_ {lo.shape} and max_ {hi.shape} are not 36 values each")
+    return lo.reshape(-1), hi.reshape(-1)
+
+
+def load_brisque_params(model_path, range_path) -> BrisqueParams:
+    """model_path: the libsvm text model of imquality's BRISQUE (svm_type epsilon_svr, kernel_type rbf, gamma, total_sv, rho, SV,
+    then `coef index:value ...` lines with 1-based indices, an absent index being 0).  range_path: its normalize.pickle (min_,
+    max_) or an .npz with those keys.  Neither file is shipped: both are the user's own.  Anything else raises ValueError."""
+    if model_path is None or range_path is None:
+        raise ValueError(_BRISQUE_NO_PARAMS)
+    sv, coef, rho, gamma = _brisque_model(model_path)
+    lo, hi = _brisque_range(range_path)
+    return BrisqueParams(sv, coef, rho, gamma, lo, hi)
+
+
+def _brisque_params(params) -> BrisqueParams:
+    if isinstance(params, BrisqueParams):
+        return params
+    if isinstance(params, (tuple, list)) and len(params) == 2:
+        return load_brisque_params(*params)
+    raise ValueError(_BRISQUE_NO_PARAMS)
+
+
+def brisque_plan(h: int, w: int) -> dict:
+    """cidnet_metric_brisque_plan (host only): tile side, tile rows / columns at both scales, the half size, the tile
+    kernel's LDS bytes and the workspace floats per image"""
+    buf = (ctypes.c_int * 9)()
+    lib().call("cidnet_metric_brisque_plan", int(h), int(w), buf, 9)
+    return dict(zip(("tile", "tiles_y", "tiles_x", "h2", "w2", "tiles_y2", "tiles_x2", "lds", "ws_floats"), buf))
+
+
+def _brisque_input(q, what):
+    if not isinstance(q, torch.Tensor):
+        raise RuntimeError(f"{what}: expected a tensor")
+    _on_device(q)
+    if q.dtype != torch.uint8:
+        raise RuntimeError(f"{what} takes uint8 images (got {q.dtype}); see to_uint8")
+    x = _batched(q, what)
+    h, w = x.shape[-2:]
+    if h < BRISQUE_MIN or w < BRISQUE_MIN:
+        raise ValueError(f"{what}: images of at least {BRISQUE_MIN} x {BRISQUE_MIN} pixels are needed (got {h} x {w})")
+    return x
+
+
+def _brisque_plane(y, what, least):
+    if not isinstance(y, torch.Tensor):
+        raise RuntimeError(f"{what}: expected a tensor")
+    _on_device(y)
+    if y.dtype != torch.float64:
+        raise RuntimeError(f"{what}: expected an fp64 plane (got {y.dtype})")
+    if y.dim() == 2:
+        y = y.unsqueeze(0)
+    if y.dim() != 3:
+        raise RuntimeError(f"{what}: expected (B,h,w) or (h,w), got {tuple(y.shape)}")
+    if y.shape[1] < least or y.shape[2] < least:
+        raise ValueError(f"{what}: planes of at least {least} x {least} are needed (got {y.shape[1]} x {y.shape[2]})")
+    return y.contiguous()
+
+
+def brisque_gray(q: torch.Tensor) -> torch.Tensor:
+    """uint8 (B,3,h,w) (or (3,h,w)) on the device -> fp64 (B,h,w): (0.2125 R + 0.7154 G + 0.0721 B) / 255, skimage's rgb2gray of
+    a uint8 image.  A stage of brisque_features."""
+    x = _brisque_input(q, "brisque_gray")
+    B, _, h, w = x.shape
+    y = torch.empty((B, h, w), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        lib().call("cidnet_metric_brisque_gray", ops._p(x), ops._p(y), B, h, w, ops._stream())
+    return y
+
+
+def brisque_half(y: torch.Tensor) -> torch.Tensor:
+    """fp64 (B,h,w) (or (h,w)) -> fp64 (B, round(h/2), round(w/2)) (half to even): skimage.transform.rescale(y, 1/2) with its
+    defaults, restated as scipy's gaussian_filter(sigma 0.5, mirror) and zoom(order 1, grid mode).  The stage of
+    brisque_features that is least certain to match imquality's, and the one to replace if it does not."""
+    x = _brisque_plane(y, "brisque_half", BRISQUE_MIN)
+    B, h, w = x.shape
+    p = brisque_plan(h, w)
+    tmp = torch.empty((2, B, h, w), dtype=torch.float64, device=x.device)
+    out = torch.empty((B, p["h2"], p["w2"]), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        lib().call("cidnet_metric_brisque_half", ops._p(x), ops._p(tmp), ops._p(out), B, h, w, ops._stream())
+    return out
+
+
+def brisque_mscn(y: torch.Tensor):
+    """fp64 gray plane (B,h,w) (or (h,w)), or uint8 images (B,3,h,w) whose gray value is formed on the way -> (mscn fp64 (B,h,w),
+    moments fp64 (B,tiles,5,6)): the locally normalised image (7 x 7 Gaussian of sigma 7/6, zero fill) and, per 32 x 32 tile
+    in row-major order and per map (M, and M times its right, lower, lower-right and lower-left neighbour, where that exists),
+    the count and sum of squares of the negatives, the same of the elements >= 0, sum |v| and sum v^2.  A stage of
+    brisque_features."""
+    rgb = isinstance(y, torch.Tensor) and y.dtype == torch.uint8
+    x = _brisque_input(y, "brisque_mscn") if rgb else _brisque_plane(y, "brisque_mscn", BRISQUE_MIN // 2)
+    B, h, w = x.shape[0], x.shape[-2], x.shape[-1]
+    tiles = -(-h // 32) * -(-w // 32)
+    m = torch.empty((B, h, w), dtype=torch.float64, device=x.device)
+    mom = torch.empty((B, tiles, 5, 6), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        lib().call("cidnet_metric_brisque_moments", ops._p(x), int(not rgb), ops._p(m), ops._p(mom), B, h, w, ops._stream())
+    return m, mom
+
+
+def brisque_fit(moments: torch.Tensor) -> torch.Tensor:
+    """moments fp64 (B,tiles,5,6) -> the 18 features of one scale (B,18) fp64: the tiles' sums added in a fixed order and the
+    asymmetric generalised Gaussian fitted to each map, its shape the root of the moment ratio in [0.05, 100].  A map with an
+    empty side or no variance gives NaN.  A stage of brisque_features."""
+    _on_device(moments)
+    if moments.dtype != torch.float64 or moments.dim() != 4 or tuple(moments.shape[-2:]) != (5, 6) or moments.shape[1] < 1:
+        raise RuntimeError(f"brisque_fit: expected fp64 (B,tiles,5,6) moments, got {moments.dtype} {tuple(moments.shape)}")
+    mom = moments.contiguous()
+    B, tiles = mom.shape[:2]
+    feat = torch.empty((B, 18), dtype=torch.float64, device=mom.device)
+    with torch.cuda.device(mom.device):
+        lib().call("cidnet_metric_brisque_fit", ops._p(mom), tiles, ops._p(feat), 18, B, ops._stream())
+    return feat
+
+
+def brisque_features(q: torch.Tensor) -> torch.Tensor:
+    """uint8 (B,3,h,w) (or (3,h,w)) on the device, h, w >= 16 -> (B,36) fp64 on the device: the 18 features of the gray image and
+    the 18 of its half-size version, per scale [alpha, variance] of M and [alpha, mean, left variance, right variance] of H, V,
+    D1, D2 (include/cidnet_hip.h: BRISQUE).  NaN where a fit has an empty side or no variance -- an exactly flat image."""
+    x = _brisque_input(q, "brisque_features")
+    B, _, h, w = x.shape
+    n = lib().raw("cidnet_metric_brisque_ws_floats")(B, h, w)
+    if n <= 0:
+        raise ValueError(f"brisque_features: {B} images of {h} x {w} are outside the kernels' limits (h w <= 2^26, B <= 65535)")
+    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+    feat = torch.empty((B, BRISQUE_FEATURES), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        lib().call("cidnet_metric_brisque_features", ops._p(x), ops._p(feat), ops._p(ws), n, B, h, w, ops._stream())
+    return feat
+
+
+def brisque_score(features: torch.Tensor, params) -> torch.Tensor:
+    """(B,36) fp64 features on the device -> (B,) fp64 on the device: the features scaled to [-1, 1] by the model's ranges, then
+    libsvm's epsilon-SVR decision sum_i coef_i exp(-gamma |sv_i - z|^2) - rho over the support vectors in file order.
+    params: a BrisqueParams or the (model, range) pair of paths.  NaN features give NaN."""
+    prm = _brisque_params(params)
+    if not isinstance(features, torch.Tensor):
+        raise RuntimeError("brisque_score: expected a tensor")
+    _on_device(features)
+    if features.dtype != torch.float64 or features.dim() != 2 or features.shape[1] != BRISQUE_FEATURES or features.shape[0] < 1:
+        raise RuntimeError(f"brisque_score: expected fp64 (B,36) features, got {features.dtype} {tuple(features.shape)}")
+    f = features.contiguous()
+    sv, coef, fmin, fmax, rg = prm.on(f.device)
+    out = torch.empty(f.shape[0], dtype=torch.float64, device=f.device)
+    with torch.cuda.device(f.device):
+        lib().call("cidnet_metric_brisque_svr", ops._p(f), ops._p(sv), ops._p(coef), ops._p(fmin), ops._p(fmax), ops._p(rg),
+                   coef.shape[0], ops._p(out), f.shape[0], ops._stream())
+    return out
+
+
+def brisque(q_u8: torch.Tensor, params) -> torch.Tensor:
+    """uint8 (B,3,h,w) (or (3,h,w)) on the device -> (B,) fp64 on the device, no host synchronisation: the BRISQUE score of each
+    image as imquality.brisque.score states it (measure_niqe_bris.py:26), restated stage by stage from that package's
+    description and pinned to scipy / scikit-learn, not to imquality itself.  params: a BrisqueParams or the
+    (libsvm model, range file) pair of paths -- the user's own files.  An exactly flat image scores NaN; in a partly flat one the
+    side of zero its rounding noise falls on follows the summation order, here as on the host."""
+    prm = _brisque_params(params)
+    return brisque_score(brisque_features(q_u8), prm)

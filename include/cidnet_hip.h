@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 25
+#define CIDNET_ABI_VERSION 26
 
 int cidnet_abi_version(void);
 
@@ -993,6 +993,58 @@ int cidnet_metric_ciede2000_plan(int h, int w, int* out, int n);
 int cidnet_metric_ciede2000_u8(const uint8_t* restored, const uint8_t* gt, const double* scale, const double* lin_table, double* map,
                                double* mean, void* ws, long ws_bytes, int B, int h, int w, void* stream);
 int cidnet_metric_ciede2000_lab(const double* lab1, const double* lab2, double* out, long n, void* stream);
+
+/* ---- BRISQUE (csrc/brisque.hip): the second number measure_niqe_bris.py prints per unpaired set, imquality.brisque.score of
+ * the saved output.  imquality, scikit-image, cv2 and libsvm are not at hand: the stages are restated from the description of
+ * that package, and parity with it is NOT pinned; every stage is pinned to the scipy / scikit-learn routine named with it
+ * (tests/brisque_ref.py).  All arithmetic fp64, no fused multiply-add, no atomics, fixed reduction order:
+ * bit-identical from call to call, and an image's values do not depend on the rest of the batch.
+ * gray: rgb planar uint8 (B,3,h,w) -> y (B,h,w) doubles, Y = ((0.2125 R + 0.7154 G) + 0.0721 B) / 255 (skimage's rgb2gray).
+ * half: y (B,h,w) -> out (B,h2,w2), h2 = round(h / 2), w2 = round(w / 2) with numpy's rounding, half to even (17 x 23 -> 8 x 12):
+ *   skimage.transform.rescale(y, 1/2) with its defaults -- the Gaussian of sigma 0.5 cut at radius 2 with a mirrored border
+ *   (-1 -> 1), down the columns and then along the rows, each pass k0 x + k1 (x[-1] + x[+1]) + k2 (x[-2] + x[+2])
+ *   (scipy.ndimage.gaussian_filter(y, 0.5, mode='mirror')), then order-1 resampling at (o + 0.5) n_in / n_out - 0.5 on both
+ *   axes, the row pair first: (1 - ty) ((1 - tx) a00 + tx a01) + ty ((1 - tx) a10 + tx a11) (scipy.ndimage.zoom(order=1,
+ *   mode='mirror', grid_mode=True)).  tmp: 2 B h w doubles of scratch.  A stage of its own so that another resampler is a
+ *   local change.
+ * moments: img is rgb (B,3,h,w) uint8 (img_f64 == 0: the gray value is formed while staging) or a gray plane (B,h,w) doubles
+ *   (img_f64 != 0).  MSCN: mu = K * Y, s = K * Y^2, K[i][j] ~ exp(-((i-3)^2 + (j-3)^2) / (2 (7/6)^2)), 7 x 7, sum 1, ZERO outside
+ *   the image, the 49 products added in row-major order (scipy.signal.convolve2d(.., 'same')); dev = sqrt(|mu^2 - s|);
+ *   M = (Y - mu) / (dev + 1/255).  Five maps: M; H = M[r][c] M[r][c+1]; V = M[r][c] M[r+1][c]; D1 = M[r][c] M[r+1][c+1];
+ *   D2 = M[r][c] M[r+1][c-1] -- slices, not rolls: a pair whose partner lies outside the image does not exist.  The plane is cut
+ *   into 32 x 32 tiles in row-major order, tiles = ceil(h / 32) ceil(w / 32); a pair belongs to the tile of its M[r][c].
+ *   moments (B,tiles,5,6) doubles, per tile and map: the count and the sum of squares of the elements < 0, the same of the
+ *   elements >= 0 (zeros count there), sum |v|, sum v^2; counts are exact.  In a tile, thread t of 256 adds pixels t, t + 256,
+ *   t + 512, t + 768 of the row-major tile in that order, then the butterfly of each wave and the four waves in order.
+ *   mscn (optional, (B,h,w) doubles) receives M; without it the map never leaves the compute unit.
+ * fit: moments (B,tiles,5,6) -> 18 features at feat + b feat_stride.  Per map the tile slots are added by lane l of 64 over
+ *   tiles l, l + 64, ... in that order and then by the butterfly; with nl, Sl, nr, Sr, A, Q the six sums: sl = sqrt(Sl / nl),
+ *   sr = sqrt(Sr / nr), g = sl / sr, n = nl + nr, r = (A / n)^2 / (Q / n), R = r (g^3 + 1)(g + 1) / (g^2 + 1)^2, alpha the root of
+ *   phi(a) = exp(2 lgamma(2/a) - lgamma(1/a) - lgamma(3/a)) = R in [0.05, 100], bracketed 65 ways per round until the fp64
+ *   bracket stops moving, alpha = (lo + hi) / 2 (oracle: scipy.optimize.brentq, xtol 1e-15); c = sqrt(Gamma(1/alpha) /
+ *   Gamma(3/alpha)), mean = (sr - sl) c Gamma(2/alpha) / Gamma(1/alpha).  Features: M gives [alpha, (sl^2 + sr^2) / 2], each
+ *   product map [alpha, mean, sl^2, sr^2], in the order M, H, V, D1, D2.  R outside (phi(0.05), phi(100)) or NaN (an empty side,
+ *   no variance) makes all of that map's features NaN; nothing is raised.
+ * svr: feat (B,36) -> score (B): z = -1 + 2 (f - fmin) / (fmax - fmin), score = sum_i coef[i] exp(-gamma |sv[i] - z|^2) - rho, the
+ *   squared distance over the 36 features in order, the sum over the n_sv support vectors (sv (n_sv,36)) in order, by one
+ *   thread.  rho_gamma: {rho, gamma}, two doubles on the device.
+ * features: all of the above for rgb (B,3,h,w): feat (B,36) = the 18 features at full size | the 18 at half size.
+ *   ws: cidnet_metric_brisque_ws_floats(B, h, w) floats, 8-byte aligned.
+ * plan: host only, launches nothing; the function the launchers' sizes come from.  Writes out[0..8] = tile side, tile rows and
+ *   tile columns at full size, h2, w2, tile rows and tile columns at half size, static LDS bytes of the tile kernel, workspace
+ *   floats per image.  out NULL or n < 9 is CIDNET_ERR_ARG and nothing is written; never writes past out[8].
+ * Errors: a NULL pointer (but mscn), a pointer to doubles that is not 8-byte aligned, B, h, w, tiles or n_sv < 1 is
+ *   CIDNET_ERR_ARG; h or w < 16 (moments alone: < 8, the half-size plane of the smallest image), h w > 2^26, B > 65535 or
+ *   feat_stride < 18 CIDNET_ERR_SHAPE; a short workspace CIDNET_ERR_WS.  ws_floats is 0 for sizes the launcher rejects. */
+int cidnet_metric_brisque_plan(int h, int w, int* out, int n);
+long cidnet_metric_brisque_ws_floats(int B, int h, int w);
+int cidnet_metric_brisque_gray(const uint8_t* rgb, double* y, int B, int h, int w, void* stream);
+int cidnet_metric_brisque_half(const double* y, double* tmp, double* out, int B, int h, int w, void* stream);
+int cidnet_metric_brisque_moments(const void* img, int img_f64, double* mscn, double* moments, int B, int h, int w, void* stream);
+int cidnet_metric_brisque_fit(const double* moments, int tiles, double* feat, int feat_stride, int B, void* stream);
+int cidnet_metric_brisque_svr(const double* feat, const double* sv, const double* coef, const double* fmin, const double* fmax,
+                              const double* rho_gamma, int n_sv, double* score, int B, void* stream);
+int cidnet_metric_brisque_features(const uint8_t* rgb, double* feat, float* ws, long ws_floats, int B, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }
