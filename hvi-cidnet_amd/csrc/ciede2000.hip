@@ -23,6 +23,7 @@
 
 #include "cidnet_hip.h"
 #include "common.h"
+#include "gt_mean.h"
 
 namespace cidnet {
 namespace {
@@ -156,10 +157,7 @@ __global__ __launch_bounds__(kThreads) void ciede_u8_kernel(const uint8_t* __res
     if (SCALED) {
       double v[3];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const double t = (double)((w[c] >> sh) & 255u) * s;                       // a NaN scale propagates, as np.clip does
-        v[c] = linear_of((t < 0.0 ? 0.0 : (t > 255.0 ? 255.0 : t)) / 255.0);
-      }
+      for (int c = 0; c < 3; ++c) v[c] = linear_of(gt_mean_value((w[c] >> sh) & 255u, s) / 255.0);
       p = lab_of_linear(v[0], v[1], v[2]);
     } else {
       p = lab_of_linear(lin[(w[0] >> sh) & 255u], lin[(w[1] >> sh) & 255u], lin[(w[2] >> sh) & 255u]);

@@ -24,6 +24,7 @@
 // rounding residual of one product and identical images would not score exactly 0.
 #include "common.h"
 #include "cidnet_hip.h"
+#include "gt_mean.h"
 
 namespace cidnet {
 namespace {
@@ -34,7 +35,6 @@ constexpr int kConvThreads = 256;
 constexpr int kARows = kConvThreads / kKC;                     // weight rows one staging pass covers
 constexpr int kAIter = kMT / kARows, kBIter = kKC / 4;         // staged values per thread and chunk: weights, im2col
 constexpr int kDistThreads = 256, kDistPix = 32, kDistGroups = kDistThreads / kDistPix;
-constexpr int kGrayChunk = 16384, kGrayThreads = 256;          // as csrc/metrics.hip: the same sums, the same ratio
 
 struct LpipsSizes {
   int fh[5], fw[5];
@@ -58,60 +58,6 @@ inline int lpips_channels(int l) {
   return c[l];
 }
 inline long dist_blocks(long P) { return (P + kDistPix - 1) / kDistPix; }
-inline long gray_chunks(long hw) { return (hw + kGrayChunk - 1) / kGrayChunk; }
-
-__device__ __forceinline__ unsigned gray601(unsigned r, unsigned g, unsigned b) {
-  return (4899u * r + 9617u * g + 1868u * b + 8192u) >> 14;
-}
-
-// gray sums of both images of each pair, per chunk of pixels (exact: integers)
-__global__ __launch_bounds__(kGrayThreads) void lpips_gray_sum_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
-                                                                      unsigned long long* __restrict__ part, long hw, int n_chunk) {
-  __shared__ unsigned red[2][kGrayThreads / 64];
-  const long img = blockIdx.y;
-  const uint8_t* pa = a + img * 3 * hw;
-  const uint8_t* pb = b + img * 3 * hw;
-  const long i0 = (long)blockIdx.x * kGrayChunk;
-  const long i1 = i0 + kGrayChunk < hw ? i0 + kGrayChunk : hw;
-  unsigned sa = 0, sb = 0;                                       // <= 16384 * 255 per block
-  for (long i = i0 + threadIdx.x; i < i1; i += kGrayThreads) {
-    sa += gray601(pa[i], pa[i + hw], pa[i + 2 * hw]);
-    sb += gray601(pb[i], pb[i + hw], pb[i + 2 * hw]);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sa += __shfl_xor(sa, o, 64);
-    sb += __shfl_xor(sb, o, 64);
-  }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[0][wv] = sa;
-    red[1][wv] = sb;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long ta = 0, tb = 0;
-    for (int k = 0; k < kGrayThreads / 64; ++k) {
-      ta += red[0][k];
-      tb += red[1][k];
-    }
-    part[((long)img * n_chunk + blockIdx.x) * 2 + 0] = ta;
-    part[((long)img * n_chunk + blockIdx.x) * 2 + 1] = tb;
-  }
-}
-
-// s = (sum_gt / N) / (sum_restored / N), one lane per image: the expression of csrc/metrics.hip, so the same bits
-__global__ void lpips_scale_kernel(const unsigned long long* __restrict__ part, int n_chunk, double n_pix, double* __restrict__ scale,
-                                   int B) {
-  const int img = blockIdx.x * blockDim.x + threadIdx.x;
-  if (img >= B) return;
-  unsigned long long ta = 0, tb = 0;
-  for (int k = 0; k < n_chunk; ++k) {
-    ta += part[((long)img * n_chunk + k) * 2 + 0];
-    tb += part[((long)img * n_chunk + k) * 2 + 1];
-  }
-  scale[img] = ((double)tb / n_pix) / ((double)ta / n_pix);
-}
 
 __global__ __launch_bounds__(256) void lpips_ingest_kernel(const uint8_t* __restrict__ q, const double* __restrict__ scale,
                                                            float* __restrict__ x, long hw, long total) {
@@ -121,10 +67,7 @@ __global__ __launch_bounds__(256) void lpips_ingest_kernel(const uint8_t* __rest
   const long plane = i / hw;
   const int c = (int)(plane % 3);
   double u = (double)q[i];
-  if (scale) {                                                   // clip(u s, 0, 255): a NaN scale propagates as np.clip does
-    const double v = u * scale[plane / 3];
-    u = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
-  }
+  if (scale) u = gt_mean_value(q[i], scale[plane / 3]);
   const float v = (float)(u / 127.5 - 1.0);                      // fp64, rounded once
   x[i] = (v - shift[c]) / scl[c];                                // the scaling layer, fp32
 }
@@ -319,28 +262,6 @@ int cidnet_lpips_feature_sizes(int h, int w, int* sizes) {
     sizes[2 * l] = s.fh[l];
     sizes[2 * l + 1] = s.fw[l];
   }
-  return CIDNET_OK;
-}
-
-long cidnet_metric_lpips_scale_ws_floats(int B, int h, int w) {
-  if (B <= 0 || h <= 0 || w <= 0) return 0;
-  return 2 * (long)B * gray_chunks((long)h * w) * 2;
-}
-
-int cidnet_metric_lpips_scale(const uint8_t* restored, const uint8_t* gt, double* scale, float* ws, long ws_floats, int B, int h,
-                              int w, void* stream) {
-  CIDNET_CHECK_ARG(restored && gt && scale && ws && B > 0 && h > 0 && w > 0);
-  if (B > 65535) return CIDNET_ERR_SHAPE;
-  if (ws_floats < cidnet_metric_lpips_scale_ws_floats(B, h, w)) return CIDNET_ERR_WS;
-  hipStream_t st = (hipStream_t)stream;
-  const long hw = (long)h * w;
-  const long n_chunk = gray_chunks(hw);
-  unsigned long long* gpart = reinterpret_cast<unsigned long long*>(ws);
-  hipLaunchKernelGGL(lpips_gray_sum_kernel, dim3((unsigned)n_chunk, (unsigned)B), dim3(kGrayThreads), 0, st, restored, gt, gpart, hw,
-                     (int)n_chunk);
-  CIDNET_LAUNCH_STATUS();
-  hipLaunchKernelGGL(lpips_scale_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, gpart, (int)n_chunk, (double)hw, scale, B);
-  CIDNET_LAUNCH_STATUS();
   return CIDNET_OK;
 }
 

@@ -4,7 +4,9 @@
 //   SSIM:      per colour plane, 11 x 11 Gaussian window (sigma 1.5) over the valid region only, C1 = (0.01 255)^2,
 //              C2 = (0.03 255)^2, mean of the map per plane, mean of the three planes           (measure.py:23-64)
 //   GT mean:   s = mean(gray(gt)) / mean(gray(restored)), restored -> clip(restored * s, 0, 255) in fp64 (measure.py:138-141);
-//              gray = the BT.601 fixed-point rule (4899 R + 9617 G + 1868 B + 8192) >> 14 on uint8, summed exactly.
+//              gray = the BT.601 fixed-point rule (4899 R + 9617 G + 1868 B + 8192) >> 14 on uint8, summed exactly.  The scale
+//              is formed once (cidnet_metric_gt_mean_scale, below) and handed to every paired metric: PSNR/SSIM here,
+//              csrc/lpips.hip and csrc/ciede2000.hip; gray and the clip are csrc/gt_mean.h.
 // Arithmetic is fp64 as the reference's; the squared error sums are exact (integers, or products of fp32 values in fp64).
 // Reductions: per-block partials written to fixed slots, summed by a per-image finishing kernel in a fixed order, so a
 // result is bit-identical from call to call and does not depend on which other images share the batch.
@@ -15,6 +17,7 @@
 // registers, and an output row is complete (and its SSIM formed) when the input row five below it has been added.
 #include "common.h"
 #include "cidnet_hip.h"
+#include "gt_mean.h"
 
 namespace cidnet {
 namespace {
@@ -39,16 +42,6 @@ inline Gauss64 make_gauss64() {                  // exp(-(i-5)^2 / (2 1.5^2)), n
   }
   for (int i = 0; i < kWin; ++i) w.g[i] = w.g[i] / s;
   return w;
-}
-
-// clip(a * s, 0, 255) in fp64 (a NaN scale -- an all-black restored image -- propagates as np.clip does)
-__device__ __forceinline__ double gt_mean_value(unsigned a, double s) {
-  const double v = (double)a * s;
-  return v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
-}
-
-__device__ __forceinline__ unsigned gray601(unsigned r, unsigned g, unsigned b) {
-  return (4899u * r + 9617u * g + 1868u * b + 8192u) >> 14;
 }
 
 __global__ __launch_bounds__(256) void to_uint8_kernel(const float* __restrict__ x, uint8_t* __restrict__ q, long total, int Hp,
@@ -246,36 +239,48 @@ int cidnet_metric_to_uint8(const float* x, uint8_t* q, int B, int Hp, int Wp, in
   return CIDNET_OK;
 }
 
-// layout (8-byte words): scale[B] | gray partials [B][chunks][2] | tile partials [B][3][tiles][2]
-long cidnet_metric_ws_floats(int B, int h, int w) {
+// 8-byte words: gray partials [B][chunks][2]
+long cidnet_metric_gt_mean_scale_ws_floats(int B, int h, int w) {
   if (B <= 0 || h <= 0 || w <= 0) return 0;
-  const long words = B + (long)B * gray_chunks((long)h * w) * 2 + (long)B * 3 * tiles_per_plane(h, w) * 2;
-  return 2 * words;
+  return 2 * (long)B * gray_chunks((long)h * w) * 2;
 }
 
-int cidnet_metric_psnr_ssim(const uint8_t* restored, const uint8_t* gt, int gt_mean, double* psnr, double* ssim, float* ws,
+int cidnet_metric_gt_mean_scale(const uint8_t* restored, const uint8_t* gt, double* scale, float* ws, long ws_floats, int B, int h,
+                                int w, void* stream) {
+  CIDNET_CHECK_ARG(restored && gt && scale && ws && B > 0 && h > 0 && w > 0);
+  if (B > 65535) return CIDNET_ERR_SHAPE;
+  if (ws_floats < cidnet_metric_gt_mean_scale_ws_floats(B, h, w)) return CIDNET_ERR_WS;
+  hipStream_t st = (hipStream_t)stream;
+  const long hw = (long)h * w;
+  const long n_chunk = gray_chunks(hw);
+  unsigned long long* gpart = reinterpret_cast<unsigned long long*>(ws);
+  hipLaunchKernelGGL(gray_sum_kernel, dim3((unsigned)n_chunk, (unsigned)B), dim3(kGrayThreads), 0, st, restored, gt, gpart, hw,
+                     (int)n_chunk);
+  CIDNET_LAUNCH_STATUS();
+  hipLaunchKernelGGL(gt_mean_scale_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, gpart, (int)n_chunk, (double)hw,
+                     scale, B);
+  CIDNET_LAUNCH_STATUS();
+  return CIDNET_OK;
+}
+
+// 8-byte words: tile partials [B][3][tiles][2]
+long cidnet_metric_ws_floats(int B, int h, int w) {
+  if (B <= 0 || h <= 0 || w <= 0) return 0;
+  return 2 * ((long)B * 3 * tiles_per_plane(h, w) * 2);
+}
+
+int cidnet_metric_psnr_ssim(const uint8_t* restored, const uint8_t* gt, const double* scale, double* psnr, double* ssim, float* ws,
                             long ws_floats, int B, int h, int w, void* stream) {
   CIDNET_CHECK_ARG(restored && gt && (psnr || ssim) && ws && B > 0 && h > 0 && w > 0);
   if (ssim && (h < kWin || w < kWin)) return CIDNET_ERR_SHAPE;     // the valid region would be empty
   if (ws_floats < cidnet_metric_ws_floats(B, h, w)) return CIDNET_ERR_WS;
   hipStream_t st = (hipStream_t)stream;
   const long hw = (long)h * w;
-  const long n_chunk = gray_chunks(hw);
-  double* scale = reinterpret_cast<double*>(ws);
-  unsigned long long* gpart = reinterpret_cast<unsigned long long*>(scale + B);
-  double* tpart = reinterpret_cast<double*>(gpart + (long)B * n_chunk * 2);
-  if (gt_mean) {
-    hipLaunchKernelGGL(gray_sum_kernel, dim3((unsigned)n_chunk, (unsigned)B), dim3(kGrayThreads), 0, st, restored, gt, gpart, hw,
-                       (int)n_chunk);
-    CIDNET_LAUNCH_STATUS();
-    hipLaunchKernelGGL(gt_mean_scale_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, gpart, (int)n_chunk, (double)hw,
-                       scale, B);
-    CIDNET_LAUNCH_STATUS();
-  }
+  double* tpart = reinterpret_cast<double*>(ws);
   const dim3 grid((unsigned)((w + kTW - 1) / kTW), (unsigned)((h + kTH - 1) / kTH), (unsigned)(B * 3));
   const Gauss64 g = make_gauss64();
-  if (gt_mean && ssim) hipLaunchKernelGGL((metric_tile_kernel<true, true>), grid, dim3(64), 0, st, restored, gt, scale, g, tpart, h, w);
-  else if (gt_mean) hipLaunchKernelGGL((metric_tile_kernel<true, false>), grid, dim3(64), 0, st, restored, gt, scale, g, tpart, h, w);
+  if (scale && ssim) hipLaunchKernelGGL((metric_tile_kernel<true, true>), grid, dim3(64), 0, st, restored, gt, scale, g, tpart, h, w);
+  else if (scale) hipLaunchKernelGGL((metric_tile_kernel<true, false>), grid, dim3(64), 0, st, restored, gt, scale, g, tpart, h, w);
   else if (ssim) hipLaunchKernelGGL((metric_tile_kernel<false, true>), grid, dim3(64), 0, st, restored, gt, scale, g, tpart, h, w);
   else hipLaunchKernelGGL((metric_tile_kernel<false, false>), grid, dim3(64), 0, st, restored, gt, scale, g, tpart, h, w);
   CIDNET_LAUNCH_STATUS();

@@ -6,6 +6,7 @@ also writes the files eval.py writes (image_io's egress kernel and writer), whic
     q = M.to_uint8(rgb, size=(h, w))        # fp32 (B,3,Hp,Wp) -> uint8 (B,3,h,w): clamp, x255, truncate, crop
     r = M.resize_u8(q, (h2, w2))            # uint8 (B,3,h,w) -> uint8 (B,3,h2,w2): PIL's Image.resize, byte for byte
     p = M.psnr(q, gt_u8, gt_mean=False)     # (B,) float64 on the device, no host synchronisation
+    k = M.gt_mean_scale(q, gt_u8)           # (B,) float64 on the device: the GT-mean scale every gt_mean=True uses
     s = M.ssim(q, gt_u8, gt_mean=False)     # (B,) float64 on the device
     res = M.evaluate(model, pairs, gamma=1.0, gated=False, alpha_s=1.3, gated2=False, alpha=1.0, batch_size=1, save_dir=None,
                      resize=False, lpips=None, ciede2000=False)
@@ -229,22 +230,57 @@ def _u8_pair(who, restored, gt):
     return a, g
 
 
+def _checked_scale(who, scale, B, device):
+    """a caller's GT-mean scale -> (B,) float64, contiguous, on `device`"""
+    if scale.dtype != torch.float64 or tuple(scale.shape) != (B,):
+        raise RuntimeError(f"{who}: scale must be ({B},) float64 (got {tuple(scale.shape)} {scale.dtype})")
+    _on_device(scale)
+    if scale.device != device:
+        raise RuntimeError(f"{who}: scale is on {scale.device}, the images on {device}")
+    return scale.contiguous()
+
+
+def _gt_mean_scale(a, g):
+    """gt_mean_scale() of a checked (B,3,h,w) pair.  The caller has made the device current."""
+    B, _, h, w = a.shape
+    n = lib().raw("cidnet_metric_gt_mean_scale_ws_floats")(B, h, w)
+    ws = torch.empty(n, dtype=torch.float32, device=a.device)
+    s = torch.empty(B, dtype=torch.float64, device=a.device)
+    lib().call("cidnet_metric_gt_mean_scale", ops._p(a), ops._p(g), ops._p(s), ops._p(ws), n, B, h, w, ops._stream())
+    return s
+
+
+def gt_mean_scale(restored_u8: torch.Tensor, gt_u8: torch.Tensor) -> torch.Tensor:
+    """uint8 (B,3,h,w) (or (3,h,w)) pairs on the device -> (B,) float64 on the device, no host synchronisation: the "GT mean"
+    scale s = mean(gray(gt)) / mean(gray(restored)) of measure.py:138-141, gray the BT.601 fixed-point rule, summed exactly.
+    Every paired metric's gt_mean=True rescales `restored` to clip(restored * s, 0, 255) with this number; psnr_ssim(scale=)
+    and lpips_features(scale=) take it as it is.  An image whose gray mean is 0 gives inf or NaN.  Any h, w >= 1."""
+    a, g = _u8_pair("gt_mean_scale", restored_u8, gt_u8)
+    with torch.cuda.device(a.device):
+        return _gt_mean_scale(a, g)
+
+
 def psnr_ssim(restored: torch.Tensor, gt: torch.Tensor, gt_mean: bool = False, want_psnr: bool = True,
-              want_ssim: bool = True):
+              want_ssim: bool = True, scale=None):
     """uint8 (B,3,h,w) pairs on the device -> (psnr, ssim), each (B,) float64 on the device (None where not wanted), from one
-    pass over the images.  gt_mean: rescale `restored` by mean(gray(gt)) / mean(gray(restored)) first (measure.py:138-141),
-    on the device.  SSIM needs h, w >= 11."""
+    pass over the images.  gt_mean: rescale `restored` by gt_mean_scale(restored, gt) first (measure.py:138-141), on the
+    device.  scale: a (B,) float64 tensor on the images' device is used as that scale as it is, and implies gt_mean.  SSIM
+    needs h, w >= 11."""
     a, g = _u8_pair("psnr / ssim", restored, gt)
     B, _, h, w = a.shape
     if want_ssim and (h < 11 or w < 11):
         raise RuntimeError(f"ssim needs images of at least 11 x 11 pixels (got {h} x {w}): the 11 x 11 window's valid region "
                            "would be empty")
+    if scale is not None:
+        scale = _checked_scale("psnr_ssim", scale, B, a.device)
     n = lib().raw("cidnet_metric_ws_floats")(B, h, w)
     ws = torch.empty(n, dtype=torch.float32, device=a.device)
     p = torch.empty(B, dtype=torch.float64, device=a.device) if want_psnr else None
     s = torch.empty(B, dtype=torch.float64, device=a.device) if want_ssim else None
     with torch.cuda.device(a.device):
-        lib().call("cidnet_metric_psnr_ssim", ops._p(a), ops._p(g), int(bool(gt_mean)), ops._p(p), ops._p(s), ops._p(ws), n,
+        if scale is None and gt_mean:
+            scale = _gt_mean_scale(a, g)
+        lib().call("cidnet_metric_psnr_ssim", ops._p(a), ops._p(g), ops._p(scale), ops._p(p), ops._p(s), ops._p(ws), n,
                    B, h, w, ops._stream())
     return p, s
 
@@ -537,14 +573,17 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     lp = None if lpips is None else _lpips_params(lpips)
     gt_taps = [None, None]                          # the last batch's ground truths and their taps: shared by a sweep's values
 
-    def lpips_cols(q, g, gts):
+    def lpips_cols(q, g, s, gts):
         if gt_taps[0] is None or len(gt_taps[0]) != len(gts) or any(a is not b for a, b in zip(gt_taps[0], gts)):
             gt_taps[:] = [list(gts), None]
-        plain, gtm, gt_taps[1] = _lpips_both(q, g, lp, gt_taps[1])
+        plain, gtm, gt_taps[1] = _lpips_both(q, g, lp, s, gt_taps[1])
         return plain, gtm
 
-    def extra_cols(q, g, gts):                      # the opt-in columns, in key order
-        return (*(lpips_cols(q, g, gts) if lp else ()), *(_ciede_both(q, g) if ciede2000 else ()))
+    def cols(q, g, gts):                            # every column of one scored batch, in key order; the GT-mean scale once
+        plain = psnr_ssim(q, g)
+        s = gt_mean_scale(q, g)
+        return (*plain, *psnr_ssim(q, g, scale=s), *(lpips_cols(q, g, s, gts) if lp else ()),
+                *(_ciede_both(q, g, s) if ciede2000 else ()))
 
     def load(i, pair, device):
         x, g = _image_f32(pair[0], device), _gt_u8(pair[1], device)
@@ -557,12 +596,12 @@ def evaluate(model, pairs, gamma: float = 1.0, gated: bool = False, alpha_s: flo
     def score(q, gts):
         g = torch.stack(gts) if len(gts) > 1 else gts[0].unsqueeze(0)
         if not resize:
-            return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True), *extra_cols(q, g, gts))
+            return cols(q, g, gts)
         # the samples of a run share the ground truth's size (run_key); the flag column travels with the values, so that
         # every rank of a sharded evaluation reports the same indices
         flag = torch.full((q.shape[0],), float(q.shape[-2:] != g.shape[-2:]), dtype=torch.float64, device=q.device)
         q = resize_u8(q, g.shape[-2:])
-        return (*psnr_ssim(q, g, gt_mean=False), *psnr_ssim(q, g, gt_mean=True), *extra_cols(q, g, gts), flag)
+        return (*cols(q, g, gts), flag)
     skipped = list(getattr(pairs, "skipped", []))
 
     def result(per_image, **kw):
@@ -1260,16 +1299,6 @@ def _lpips_input(q, what):
     return x
 
 
-def _lpips_scale(a, g):
-    """(B,) fp64 on the device: mean(gray(gt)) / mean(gray(restored)), the ratio psnr_ssim(gt_mean=True) forms"""
-    B, _, h, w = a.shape
-    n = lib().raw("cidnet_metric_lpips_scale_ws_floats")(B, h, w)
-    ws = torch.empty(n, dtype=torch.float32, device=a.device)
-    s = torch.empty(B, dtype=torch.float64, device=a.device)
-    lib().call("cidnet_metric_lpips_scale", ops._p(a), ops._p(g), ops._p(s), ops._p(ws), n, B, h, w, ops._stream())
-    return s
-
-
 def _lpips_extract(parts, prm):
     """parts: [(uint8 (B_i,3,h,w), scale (B_i,) fp64 or None), ...] of one size -> the five fp32 taps of their concatenation,
     one batch through the extractor.  The caller has made the device current."""
@@ -1326,10 +1355,7 @@ def lpips_features(q_u8: torch.Tensor, params, scale=None):
     prm = _lpips_params(params)
     x = _lpips_input(q_u8, "lpips_features")
     if scale is not None:
-        _on_device(scale)
-        if scale.dtype != torch.float64 or tuple(scale.shape) != (x.shape[0],):
-            raise RuntimeError(f"lpips_features: scale must be ({x.shape[0]},) float64 (got {tuple(scale.shape)} {scale.dtype})")
-        scale = scale.contiguous()
+        scale = _checked_scale("lpips_features", scale, x.shape[0], x.device)
     with torch.cuda.device(x.device):
         return _lpips_extract([(x, scale)], prm)
 
@@ -1346,7 +1372,7 @@ def _lpips_run(restored, gt, params, gt_mean, what, want_layers, want_score):
     a, g = _lpips_pair(restored, gt, what)
     B, _, h, w = a.shape
     with torch.cuda.device(a.device):
-        f = _lpips_extract([(a, _lpips_scale(a, g) if gt_mean else None), (g, None)], prm)
+        f = _lpips_extract([(a, _gt_mean_scale(a, g) if gt_mean else None), (g, None)], prm)
         return _lpips_distance([t[:B] for t in f], [t[B:] for t in f], prm, h, w, want_layers, want_score)
 
 
@@ -1364,14 +1390,15 @@ def lpips(restored_u8: torch.Tensor, gt_u8: torch.Tensor, params, gt_mean: bool 
     return _lpips_run(restored_u8, gt_u8, params, gt_mean, "lpips", False, True)[1]
 
 
-def _lpips_both(q, g, prm, gt_feats=None):
-    """evaluate()'s LPIPS columns: (lpips, lpips_gt_mean, the ground truth's taps).  The restored and the rescaled images go
-    through the extractor as one batch; the ground truth's taps are computed unless handed in (an alpha sweep reuses them)."""
+def _lpips_both(q, g, prm, scale, gt_feats=None):
+    """evaluate()'s LPIPS columns: (lpips, lpips_gt_mean, the ground truth's taps); scale = gt_mean_scale(q, g).  The restored
+    and the rescaled images go through the extractor as one batch; the ground truth's taps are computed unless handed in (an
+    alpha sweep reuses them)."""
     B, _, h, w = q.shape
     lpips_feature_sizes(h, w)
     if gt_feats is None:
         gt_feats = _lpips_extract([(g, None)], prm)
-    f = _lpips_extract([(q, None), (q, _lpips_scale(q, g))], prm)
+    f = _lpips_extract([(q, None), (q, scale)], prm)
     plain = _lpips_distance([t[:B] for t in f], gt_feats, prm, h, w, False, True)[1]
     gtm = _lpips_distance([t[B:] for t in f], gt_feats, prm, h, w, False, True)[1]
     return plain, gtm, gt_feats
@@ -1438,7 +1465,7 @@ def _ciede_launch(a, g, scale, want_map, want_mean):
 def _ciede_run(restored, gt, gt_mean, want_map, want_mean):
     a, g = _u8_pair("ciede2000 / ciede2000_map", restored, gt)
     with torch.cuda.device(a.device):
-        return _ciede_launch(a, g, _lpips_scale(a, g) if gt_mean else None, want_map, want_mean)
+        return _ciede_launch(a, g, _gt_mean_scale(a, g) if gt_mean else None, want_map, want_mean)
 
 
 def ciede2000_map(restored_u8: torch.Tensor, gt_u8: torch.Tensor, gt_mean: bool = False) -> torch.Tensor:
@@ -1451,16 +1478,16 @@ def ciede2000(restored_u8: torch.Tensor, gt_u8: torch.Tensor, gt_mean: bool = Fa
     pixels of the CIEDE2000 difference between `restored` (colour 1) and `gt` (colour 2), each converted sRGB -> Lab with
     scikit-image's constants (D65 / 2 degree white) -- what deltaE_ciede2000(rgb2lab(a), rgb2lab(b)).mean() states, all in fp64
     (the definition: include/cidnet_hip.h, CIEDE2000).  gt_mean: `restored` enters as the real number clip(restored * s, 0,
-    255), s = mean(gray(gt)) / mean(gray(restored)) as psnr_ssim(gt_mean=True) forms it, not re-quantized (measure.py:138-141);
+    255), s = mean(gray(gt)) / mean(gray(restored)) as gt_mean_scale() forms it, not re-quantized (measure.py:138-141);
     an image whose gray mean is 0 gives whatever IEEE arithmetic makes of the infinite or NaN ratio.
     Identical images score exactly 0; a fixed-order reduction: bit-identical from call to call and independent of the rest of
     the batch (not bit-equal to ciede2000_map(...).mean(), which sums in another order).  Any h, w >= 1."""
     return _ciede_run(restored_u8, gt_u8, gt_mean, False, True)[1]
 
 
-def _ciede_both(q, g):
-    """evaluate()'s CIEDE2000 columns of a checked batch: (plain, GT mean)"""
-    return _ciede_launch(q, g, None, False, True)[1], _ciede_launch(q, g, _lpips_scale(q, g), False, True)[1]
+def _ciede_both(q, g, scale):
+    """evaluate()'s CIEDE2000 columns of a checked batch: (plain, GT mean); scale = gt_mean_scale(q, g)"""
+    return _ciede_launch(q, g, None, False, True)[1], _ciede_launch(q, g, scale, False, True)[1]
 
 
 # ---- BRISQUE (measure_niqe_bris.py:26 -> imquality.brisque.score; csrc/brisque.hip, DESIGN.md 6.17) ---------------------------

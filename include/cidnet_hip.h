@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 26
+#define CIDNET_ABI_VERSION 27
 
 int cidnet_abi_version(void);
 
@@ -597,20 +597,29 @@ int cidnet_tnsm_noise_loss(const float* noise_map, const float* out_rgb, const f
                            void* stream);
 
 /* ---- Evaluation metrics (eval.py:40-80 + measure.py:23-150 of the reference): quantize the model output, then PSNR and
- * SSIM against the ground truth, optionally after the "GT mean" rescale.  Images are uint8 (B,3,h,w) device tensors;
+ * SSIM against the ground truth, optionally after the "GT mean" rescale (gt_mean_scale).  Images are uint8 (B,3,h,w) device tensors;
  * results are one fp64 value per image in caller-owned device buffers (double* -- no host scalar, no synchronisation).
  * to_uint8: q = (uint8) trunc(clamp(x, 0, 1) * 255.0f) of the top-left h x w crop of x (B,3,Hp,Wp) (eval.py:69-73 with
  *   ToPILImage's pic.mul(255).byte(); NaN -> 0).
  * psnr_ssim: psnr[b] = 10 log10(255^2 / (mean((a - g)^2) + 1e-8)) over the 3 h w values (measure.py:66-71; squared errors
  *   summed exactly); ssim[b] = mean over the three planes of the mean SSIM map on the valid region of the 11 x 11
- *   Gaussian window (sigma 1.5), C1 = (0.01 255)^2, C2 = (0.03 255)^2, fp64 (measure.py:23-64).  gt_mean != 0: a is first
- *   replaced by clip(a * s, 0, 255) (fp64; PSNR reads its fp32 cast) with s = mean(gray(g)) / mean(gray(a)) formed on the
- *   device, gray = (4899 R + 9617 G + 1868 B + 8192) >> 14 (measure.py:138-141).  psnr or ssim may be NULL; with ssim,
- *   h < 11 or w < 11 is CIDNET_ERR_SHAPE.  Fixed-order reductions: bit-identical results from call to call, and an
- *   image's values do not depend on the rest of the batch.  ws: cidnet_metric_ws_floats(B, h, w) floats, 8-byte aligned. */
+ *   Gaussian window (sigma 1.5), C1 = (0.01 255)^2, C2 = (0.03 255)^2, fp64 (measure.py:23-64).  scale NULL: plain.  scale =
+ *   B doubles on the device (GT mean; what gt_mean_scale forms): a is first replaced by clip(a * scale[b], 0, 255) (fp64; PSNR
+ *   reads its fp32 cast).  psnr or ssim may be NULL; with ssim, h < 11 or w < 11 is CIDNET_ERR_SHAPE.  Fixed-order
+ *   reductions: bit-identical results from call to call, and an image's values do not depend on the rest of the batch.
+ *   ws: cidnet_metric_ws_floats(B, h, w) floats (the tile partials), 8-byte aligned.
+ * gt_mean_scale: the "GT mean" rescale of measure.py:138-141, formed once for every paired metric (psnr_ssim here, the LPIPS
+ *   ingest and CIEDE2000 below): scale[b] = mean(gray(gt_b)) / mean(gray(restored_b)), gray = (4899 R + 9617 G + 1868 B + 8192)
+ *   >> 14 on the 8-bit values, summed exactly in integers, then ((double) sum_gt / n) / ((double) sum_restored / n) with n = h w.
+ *   An image whose gray mean is 0 gets an infinite or NaN scale; the users clip in fp64 and let a NaN through, as np.clip
+ *   does.  Any h, w >= 1.  B > 65535 is CIDNET_ERR_SHAPE.  ws: cidnet_metric_gt_mean_scale_ws_floats(B, h, w) = 2 * B * chunks
+ *   * 2 floats (16384 pixels per chunk), 8-byte aligned. */
 int cidnet_metric_to_uint8(const float* x, uint8_t* q, int B, int Hp, int Wp, int h, int w, void* stream);
+long cidnet_metric_gt_mean_scale_ws_floats(int B, int h, int w);
+int cidnet_metric_gt_mean_scale(const uint8_t* restored, const uint8_t* gt, double* scale, float* ws, long ws_floats, int B, int h,
+                                int w, void* stream);
 long cidnet_metric_ws_floats(int B, int h, int w);
-int cidnet_metric_psnr_ssim(const uint8_t* restored, const uint8_t* gt, int gt_mean, double* psnr, double* ssim, float* ws,
+int cidnet_metric_psnr_ssim(const uint8_t* restored, const uint8_t* gt, const double* scale, double* psnr, double* ssim, float* ws,
                             long ws_floats, int B, int h, int w, void* stream);
 
 /* ---- Resize of the quantized output to the ground truth's size (measure.py:133-134, measure_SID_blur.py:91-92: im1 =
@@ -916,10 +925,8 @@ int cidnet_ensemble_merge(const float* ya, int na, const float* yb, int nb, floa
  *  (5) the smallest image is 31 x 31 (feature maps 7, 3, 1, 1, 1); anything smaller is CIDNET_ERR_SHAPE.
  * feature_sizes: host only.  sizes[2 l], sizes[2 l + 1] = height and width of tap l of an h x w image (step 2's floors);
  *   CIDNET_ERR_SHAPE under 31 in either axis.
- * scale: scale[b] = mean(gray(gt_b)) / mean(gray(restored_b)), the ratio cidnet_metric_psnr_ssim forms for GT mean (the same
- *   exact integer sums and the same fp64 expression, so the same bits).  uint8 (B,3,h,w) inputs; ws: cidnet_metric_lpips_
- *   scale_ws_floats(B, h, w) floats, 8-byte aligned.  B > 65535 is CIDNET_ERR_SHAPE.
- * ingest: step 1.  q uint8 (B,3,h,w) planar, scale NULL or B doubles on the device -> x fp32 (B,3,h,w).
+ * ingest: step 1.  q uint8 (B,3,h,w) planar, scale NULL or B doubles on the device (what cidnet_metric_gt_mean_scale forms) -> x
+ *   fp32 (B,3,h,w).
  * conv_relu: y = relu(conv(x) + bias), x (B,C,H,W), w (M,C,ksize,ksize) contiguous, y (B,M,Ho,Wo) with Ho = floor((H + 2 pad -
  *   ksize) / stride) + 1.  (ksize, stride, pad) is one of (11, 4, 2), (5, 1, 2), (3, 1, 1) and M a multiple of 64, else
  *   CIDNET_ERR_SHAPE; also when the padded input is smaller than the window, B > 65535 or a tensor of one image has more than
@@ -938,9 +945,6 @@ int cidnet_ensemble_merge(const float* ya, int na, const float* yb, int nb, floa
  *   ws: cidnet_metric_lpips_ws_floats(B, h, w) floats, 8-byte aligned, the same buffer for the five layer calls and finish;
  *   the query is host only and returns 0 for an image under 31 x 31. */
 int cidnet_lpips_feature_sizes(int h, int w, int* sizes);
-long cidnet_metric_lpips_scale_ws_floats(int B, int h, int w);
-int cidnet_metric_lpips_scale(const uint8_t* restored, const uint8_t* gt, double* scale, float* ws, long ws_floats, int B, int h,
-                              int w, void* stream);
 int cidnet_metric_lpips_ingest(const uint8_t* q, const double* scale, float* x, int B, int h, int w, void* stream);
 int cidnet_lpips_conv_relu(const float* x, const float* w, const float* bias, float* y, int B, int M, int C, int H, int W, int ksize,
                            int stride, int pad, void* stream);
@@ -969,7 +973,7 @@ int cidnet_metric_lpips_finish(const float* ws, long ws_floats, double* layers, 
  * u8: restored, gt planar uint8 (B,3,h,w), any h, w >= 1.  lin_table: 256 doubles on the device, the linear value of every
  *   level by the formula above, built by the host in fp64 (hvi-cidnet_amd/metrics.py: ciede2000_tables): no pow runs on the
  *   device for a level.  scale NULL: both sides are levels.  scale = B doubles on the device (GT mean; what
- *   cidnet_metric_lpips_scale forms): the restored pixel enters as v = clip(q scale[b], 0, 255) / 255, a real number that is not
+ *   cidnet_metric_gt_mean_scale forms): the restored pixel enters as v = clip(q scale[b], 0, 255) / 255, a real number that is not
  *   re-quantized (measure.py:138-141), through an fp64 pow; the ground truth still reads the table.  An image whose gray mean is
  *   0 has an infinite or NaN scale and gives whatever IEEE arithmetic gives.  map (B,h,w doubles) receives every pixel's dE00,
  *   mean (B doubles) the image values; either may be NULL, not both.  ws: cidnet_metric_ciede2000_ws_bytes(B, h, w) bytes,

@@ -140,6 +140,38 @@ def _case_order():
     assert sized.resized == [] and tuple(sized.per_image) == KEYS + LKEYS + CKEYS
 
 
+def test_the_gt_mean_scale_is_formed_once_per_scored_batch(dev):
+    _in_child(_case_scale_once)
+
+
+def _case_scale_once():
+    """PSNR/SSIM, LPIPS and CIEDE2000 under GT mean share one scale: the launcher runs once per scored batch and alpha"""
+    import collections
+    import hvi_cidnet_amd as P
+    from hvi_cidnet_amd import _lib
+    L = _lib.lib()
+    counts, call = collections.Counter(), L.call
+
+    def counting(name, *args):
+        counts[name] += 1
+        return call(name, *args)
+    L.call = counting
+    m, pairs, prm = _model(), _pairs(), P.LpipsParams.random()
+    # batch_size=2 over SIZES: the first two images pad alike but are cropped apart, so each is scored alone; the last two
+    # are one batch
+    scored = 3
+    res = P.evaluate(m, pairs, gated=True, batch_size=2, lpips=prm, ciede2000=True)
+    assert tuple(res.per_image) == KEYS + LKEYS + CKEYS
+    assert counts["cidnet_metric_gt_mean_scale"] == scored
+    assert counts["cidnet_metric_psnr_ssim"] == 2 * scored and counts["cidnet_metric_ciede2000_u8"] == 2 * scored
+    counts.clear()
+    alphas = [0.8, 1.0]
+    sweep = P.evaluate(m, pairs, gated2=True, alpha=alphas, batch_size=2, lpips=prm, ciede2000=True)
+    assert [r.alpha for r in sweep] == alphas
+    assert counts["cidnet_metric_gt_mean_scale"] == len(alphas) * scored
+    assert counts["cidnet_metric_psnr_ssim"] == 2 * len(alphas) * scored
+
+
 def test_two_ranks_shard_the_evaluation(dev):
     """two ranks sharing the GPU over gloo: both return exactly the single-process values"""
     got = two_ranks(_case_three)

@@ -105,7 +105,7 @@ def test_launchers_check_shapes_on_the_host():
     p = ctypes.c_void_p(256)                                       # never dereferenced: every call returns before a launch
     assert L.raw("cidnet_metric_lpips_ws_floats")(2, 400, 600) == 2 * 2 * 5 * ((99 * 149 + 31) // 32)
     assert L.raw("cidnet_metric_lpips_ws_floats")(1, 30, 31) == 0 and L.raw("cidnet_metric_lpips_ws_floats")(0, 64, 64) == 0
-    assert L.raw("cidnet_metric_lpips_scale_ws_floats")(3, 400, 600) == 2 * 3 * 15 * 2
+    assert L.raw("cidnet_metric_gt_mean_scale_ws_floats")(3, 400, 600) == 2 * 3 * 15 * 2
     sizes = (ctypes.c_int * 10)()
     assert L.raw("cidnet_lpips_feature_sizes")(31, 30, sizes) == -2
     assert L.raw("cidnet_lpips_feature_sizes")(31, 31, None) == -1
@@ -125,7 +125,8 @@ def test_launchers_check_shapes_on_the_host():
     assert L.raw("cidnet_metric_lpips_finish")(p, 10 ** 6, p, p, 1, 31, 30, None) == -2
     assert L.raw("cidnet_metric_lpips_finish")(p, 1, p, p, 1, 31, 31, None) == -3
     assert L.raw("cidnet_metric_lpips_ingest")(p, None, None, 1, 31, 31, None) == -1
-    assert L.raw("cidnet_metric_lpips_scale")(p, p, p, p, 1, 1, 31, 31, None) == -3
+    assert L.raw("cidnet_metric_gt_mean_scale")(p, p, p, p, 1, 1, 31, 31, None) == -3
+    assert L.raw("cidnet_metric_gt_mean_scale")(p, p, p, p, 10 ** 9, 70000, 31, 31, None) == -2     # gridDim.y
 
 
 def test_cpu_tensors_are_refused():

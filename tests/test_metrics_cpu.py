@@ -92,6 +92,38 @@ def test_metrics_refuse_cpu_tensors():
     assert m.training                                    # nothing was touched
 
 
+def test_psnr_ssim_launcher_checks_on_the_host():
+    import ctypes
+    from hvi_cidnet_amd import _lib
+    L = _lib.lib()
+    p = ctypes.c_void_p(256)                                       # never dereferenced: every call returns before a launch
+    # tiles of 64 x 32: 10 x 13 per plane, two 8-byte words each, counted as floats; no scale slot, no gray partials
+    assert L.raw("cidnet_metric_ws_floats")(2, 400, 600) == 2 * (2 * 3 * 10 * 13 * 2)
+    assert L.raw("cidnet_metric_ws_floats")(0, 400, 600) == 0
+    run = L.raw("cidnet_metric_psnr_ssim")
+    assert run(None, p, None, p, p, p, 10 ** 9, 1, 16, 16, None) == -1          # a plain call (scale NULL) without `restored`
+    assert run(p, p, None, None, None, p, 10 ** 9, 1, 16, 16, None) == -1       # neither result wanted
+    assert run(p, p, None, p, p, p, 1, 1, 16, 16, None) == -3                   # plain, workspace too small
+    assert run(p, p, p, p, p, p, 2 * (3 * 1 * 1 * 2) - 1, 1, 16, 16, None) == -3
+    assert run(p, p, p, p, p, p, 10 ** 9, 1, 10, 16, None) == -2                # SSIM under 11 rows
+
+
+def test_gt_mean_scale_arguments_are_checked():
+    from hvi_cidnet_amd import metrics as M
+    q = torch.zeros(2, 3, 16, 16, dtype=torch.uint8)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        M.gt_mean_scale(q, q)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        M.psnr_ssim(q, q, scale=torch.ones(2, dtype=torch.float64))
+    # the scale's own checks (the images' come first, and on this machine they are CPU tensors): dtype and length, then the device
+    dev = torch.device("cpu")
+    for bad in (torch.ones(2), torch.ones(3, dtype=torch.float64), torch.ones(2, 1, dtype=torch.float64)):
+        with pytest.raises(RuntimeError, match=r"psnr_ssim: scale must be \(2,\) float64 \(got"):
+            M._checked_scale("psnr_ssim", bad, 2, dev)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        M._checked_scale("psnr_ssim", torch.ones(2, dtype=torch.float64), 2, dev)
+
+
 def test_input_converter_accepts_and_refuses():
     """the one input converter on a CPU device: the shapes (the rounding of uint8 inputs needs the GPU: test_metrics_gpu.py)"""
     from hvi_cidnet_amd import metrics as M

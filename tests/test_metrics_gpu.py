@@ -107,6 +107,73 @@ def test_reproducible_and_batch_independent(dev):
         assert torch.equal(sub[0], first[0][1:3]) and torch.equal(sub[1], first[1][1:3])
 
 
+def _host_scale(restored, gt):
+    """the device's expression on np.float64: both gray sums are integers below 2^53, so each side does the same three
+    correctly rounded divisions and the comparison needs no tolerance"""
+    n = np.float64(restored.shape[1] * restored.shape[2])
+    ta, tb = np.float64(int(R.gray(restored).sum())), np.float64(int(R.gray(gt).sum()))
+    with np.errstate(all="ignore"):
+        return (tb / n) / (ta / n)
+
+
+@pytest.mark.parametrize("shape", [(3, 1, 1), (3, 11, 11), (3, 37, 51), (3, 128, 128), (3, 113, 145), (3, 400, 600)])
+def test_gt_mean_scale_is_bit_equal_to_the_host(dev, shape):
+    """128 x 128 is exactly one 16384-pixel chunk of the gray sum, 113 x 145 = 16385 a second chunk of one pixel"""
+    r, g = _pair(np.random.default_rng(shape[1] * 7 + shape[2]), shape)
+    s = P_M().gt_mean_scale(torch.from_numpy(r).to(dev), torch.from_numpy(g).to(dev))
+    assert s.dtype == torch.float64 and tuple(s.shape) == (1,) and s.device.type == "cuda"
+    assert np.array_equal(s.cpu().numpy(), np.array([_host_scale(r, g)]))
+
+
+def test_gt_mean_scale_batch_and_black_images(dev):
+    M = P_M()
+    rng = np.random.default_rng(14)
+    pairs = [_pair(rng, (3, 48, 70), kind) for kind in ("dark", "bright", "random")]
+    a = torch.from_numpy(np.stack([p[0] for p in pairs])).to(dev)
+    g = torch.from_numpy(np.stack([p[1] for p in pairs])).to(dev)
+    s = M.gt_mean_scale(a, g)
+    want = np.array([_host_scale(r_, g_) for r_, g_ in pairs])
+    assert len(set(want.tolist())) == 3 and np.array_equal(s.cpu().numpy(), want)
+    assert torch.equal(M.gt_mean_scale(a[1:2], g[1:2]), s[1:2])           # an image's scale does not depend on its batch
+    black = np.zeros((3, 48, 70), dtype=np.uint8)
+    rs, gs = [black, black], [pairs[0][1], black]                          # x / 0 = inf, 0 / 0 = NaN
+    s = M.gt_mean_scale(torch.from_numpy(np.stack(rs)).to(dev), torch.from_numpy(np.stack(gs)).to(dev)).cpu().numpy()
+    want = np.array([_host_scale(r_, g_) for r_, g_ in zip(rs, gs)])
+    assert np.isposinf(want[0]) and np.isnan(want[1]) and np.array_equal(s, want, equal_nan=True)
+
+
+def _mixed_batch():
+    rng = np.random.default_rng(11)                                        # test_mixed_batch_matches_the_restatement's
+    pairs = [_pair(rng, (3, 48, 70), kind) for kind in ("dark", "bright", "random")]
+    return np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+
+
+@pytest.mark.parametrize("images", [lambda: tuple(x[None] for x in _pair(np.random.default_rng(37 * 7 + 51), (3, 37, 51))),
+                                    _mixed_batch], ids=["37x51", "mixed"])
+def test_a_given_scale_is_the_gt_mean_call(dev, images):
+    M = P_M()
+    a, g = (torch.from_numpy(x).to(dev) for x in images())
+    s = M.gt_mean_scale(a, g)
+    own, given = M.psnr_ssim(a, g, gt_mean=True), M.psnr_ssim(a, g, scale=s)
+    assert torch.equal(own[0], given[0]) and torch.equal(own[1], given[1])
+    assert torch.equal(M.psnr(a, g, gt_mean=True), given[0]) and torch.equal(M.ssim(a, g, gt_mean=True), given[1])
+    assert torch.equal(M.psnr_ssim(a, g, scale=s, want_ssim=False)[0], given[0])
+    assert torch.equal(M.psnr_ssim(a, g, scale=s, want_psnr=False)[1], given[1])
+    assert not torch.equal(M.psnr_ssim(a, g)[0], given[0])                 # and a scale implies GT mean
+    B = a.shape[0]
+    for bad in (s.float(), torch.ones(B + 1, dtype=torch.float64, device=dev), s[:, None]):
+        with pytest.raises(RuntimeError, match=rf"psnr_ssim: scale must be \({B},\) float64 \(got"):
+            M.psnr_ssim(a, g, scale=bad)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        M.psnr_ssim(a, g, scale=s.cpu())
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        M.gt_mean_scale(a.cpu(), g)
+    with pytest.raises(RuntimeError, match="uint8"):
+        M.gt_mean_scale(a.float(), g.float())
+    with pytest.raises(RuntimeError, match="differ"):
+        M.gt_mean_scale(a, g[:, :, :, :20])
+
+
 def test_shape_checks(dev):
     M = P_M()
     a = torch.zeros(1, 3, 10, 40, dtype=torch.uint8, device=dev)

@@ -4,8 +4,8 @@ device events over --launches back-to-back calls, best of --reps:
   "plain_kernels" / "gt_mean_kernels": cidnet_metric_ciede2000_u8 called directly on pre-allocated outputs and workspace, the
       mean alone (the pixel launch and the finish launch: the code under test); gt_mean with a scale formed beforehand;
   "map_kernels": the same with the per-pixel map written as well (8 bytes per pixel);
-  "both": what evaluate(ciede2000=True) launches per batch -- the plain call, the scale (cidnet_metric_lpips_scale) and the
-      GT-mean call -- through the Python wrappers, allocations and argument checks included;
+  "both": the plain call, the scale (cidnet_metric_gt_mean_scale) and the GT-mean call through the Python wrappers, allocations
+      included -- evaluate(ciede2000=True)'s share of a batch, were the scale not shared with the batch's other metrics;
   "psnr_ssim": the yardstick, metrics.psnr_ssim on the same images (not the code under test).
 Each line also carries host_us_per_call, the host's time to enqueue one call: where it is close to us_per_call the device waits
 for the host and the figure is an enqueue cost, not kernel time.  One JSON line per measurement.
@@ -63,13 +63,13 @@ def main():
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
         mean = torch.empty(B, dtype=torch.float64, device=dev)
         dmap = torch.empty((B, h, w), dtype=torch.float64, device=dev)
-        scale = M._lpips_scale(q, gt)
+        scale = M.gt_mean_scale(q, gt)
 
         def kernels(s, m):
             return lambda: L.call("cidnet_metric_ciede2000_u8", ops._p(q), ops._p(gt), ops._p(s), ops._p(table), ops._p(m), ops._p(mean),
                                   ops._p(ws), nws, B, h, w, ops._stream())
         cases = (("plain_kernels", kernels(None, None)), ("gt_mean_kernels", kernels(scale, None)), ("map_kernels", kernels(None, dmap)),
-                 ("both", lambda: M._ciede_both(q, gt)), ("psnr_ssim", lambda: M.psnr_ssim(q, gt)))
+                 ("both", lambda: M._ciede_both(q, gt, M._gt_mean_scale(q, gt))), ("psnr_ssim", lambda: M.psnr_ssim(q, gt)))
         for what, fn in cases:
             us, host = timed(fn)
             print(json.dumps({"what": what, "shape": [B, h, w], "launches": a.launches, "us_per_call": us, "host_us_per_call": host,
