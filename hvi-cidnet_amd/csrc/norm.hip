@@ -78,6 +78,14 @@ template <> __device__ __forceinline__ f32x4 vrsqrt_eps<4>(f32x4 v, float invC, 
   return r;
 }
 
+// g * w kept out of FMA contraction.  The backward kernels that do not cache the product form it twice, for the channel sums
+// and again for the output; contracted into the output's subtraction the second one is unrounded, and gw - mean_c(gw) keeps
+// the product's rounding residue, which rstd (1000 on a constant column, and on every column for C = 1) amplifies.
+template <class V> __device__ __forceinline__ V mul_rounded(V a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // ---- register-resident column kernels (HW % VEC == 0) -----------------------------------------
 // w2 / bias2 / y2 (all or none): a second LayerNorm MODULE applied to the same tensor (the x-norm of one LCA block and the
 // y-norm of its partner, net/LCA.py:79,91): the normalised value is the same, so the tensor is read once and written twice
@@ -137,20 +145,24 @@ __global__ __launch_bounds__(kThreads) void ln_bwd_reg_kernel(const float* __res
     V xh[C], gw[CACHE_G ? C : 1];
 #pragma unroll
     for (int c = 0; c < C; ++c) xh[c] = Vec<VEC>::ld(xb + (long)c * HW);
-    V s1 = u * 0.f, s2 = s1;
+    // four partial sums, then a tree: one serial sum over C = 144 channels leaves five times the rounding error of a pairwise
+    // fp32 sum in gx where the terms cancel (a gradient that is constant over the channels)
+    V p1[4], p2[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { p1[k] = u * 0.f; p2[k] = p1[k]; }
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      const V g = Vec<VEC>::ld(gb + (long)c * HW) * w[c];
+      const V g = mul_rounded(Vec<VEC>::ld(gb + (long)c * HW), w[c]);
       if (CACHE_G) gw[c] = g;
       xh[c] = (xh[c] - u) * rs;
-      s1 += g;
-      s2 += g * xh[c];
+      p1[c & 3] += g;
+      p2[c & 3] += g * xh[c];
     }
-    s1 = s1 * invC; s2 = s2 * invC;
+    const V s1 = ((p1[0] + p1[1]) + (p1[2] + p1[3])) * invC, s2 = ((p2[0] + p2[1]) + (p2[2] + p2[3])) * invC;
     float* gxb = gx + b * C * HW + p;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      const V g = CACHE_G ? gw[c] : Vec<VEC>::ld(gb + (long)c * HW) * w[c];
+      const V g = CACHE_G ? gw[c] : mul_rounded(Vec<VEC>::ld(gb + (long)c * HW), w[c]);
       V o = rs * (g - s1 - xh[c] * s2);
       if (addend) o += Vec<VEC>::ld(addend + b * C * HW + p + (long)c * HW);      // gradient of the residual branch (uniform)
       Vec<VEC>::st(gxb + (long)c * HW, o);
@@ -373,7 +385,7 @@ __global__ __launch_bounds__(kThreads) void ln_bwd_kernel(const float* __restric
     const f32x4 u = ld4(mean + b * HW, p, n), rs = ld4(rstd + b * HW, p, n);
     f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1;
     for (int c = 0; c < C; ++c) {
-      const f32x4 gw = ld4(gb + (long)c * HW, p, n) * w[c];
+      const f32x4 gw = mul_rounded(ld4(gb + (long)c * HW, p, n), w[c]);
       s1 += gw;
       s2 += gw * ((ld4(xb + (long)c * HW, p, n) - u) * rs);
     }
@@ -381,7 +393,7 @@ __global__ __launch_bounds__(kThreads) void ln_bwd_kernel(const float* __restric
     float* gxb = gx + b * C * HW;
     for (int c = 0; c < C; ++c) {
       const f32x4 xh = (ld4(xb + (long)c * HW, p, n) - u) * rs;
-      f32x4 o = rs * (ld4(gb + (long)c * HW, p, n) * w[c] - s1 - xh * s2);
+      f32x4 o = rs * (mul_rounded(ld4(gb + (long)c * HW, p, n), w[c]) - s1 - xh * s2);
       if (addend) o += ld4(addend + b * C * HW + (long)c * HW, p, n);
       st4(gxb + (long)c * HW, p, n, o);
     }
