@@ -32,10 +32,13 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-
 # niqe.hip: every fp32 / fp64 rounding of the reference's pipeline is explicit there (NIQE): no implicit FMA either
 # accum.hip: gradient sum, EMA and swap are pinned bit-exact to a numpy fp32 restatement: no implicit FMA
 # lpips.hip: n(f0) - n(f1) of identical features must be exactly 0, which a fused multiply-add would spoil: no implicit FMA
+# lpips_loss.hip: the distance derivative of identical features must be exactly 0 and the float ingest pair is pinned bit for
+# bit to fp32 torch: no implicit FMA
 # ciede2000.hip: two identical pixels must give exactly 0.0, whichever way the compiler would contract the two inlined
 # sRGB -> Lab conversions of a pixel pair: no implicit FMA
 # brisque.hip: fp64 throughout, every product and sum of the stated pipeline rounded on its own (BRISQUE): no implicit FMA
 PER_FILE = {"hvi.hip": ["-ffp-contract=off"], "niqe.hip": ["-ffp-contract=off"], "accum.hip": ["-ffp-contract=off"], "lpips.hip": ["-ffp-contract=off"],
+            "lpips_loss.hip": ["-ffp-contract=off"],
             "ciede2000.hip": ["-ffp-contract=off"], "brisque.hip": ["-ffp-contract=off"], "dw.hip": ["-fno-slp-vectorize"] if not os.environ.get("CIDNET_DW_SLP") else [],
             "iel.hip": ["-fno-slp-vectorize"],
             "conv3x.hip": ["-fno-slp-vectorize", *os.environ.get("CIDNET_C3X_FLAGS", "").split()],

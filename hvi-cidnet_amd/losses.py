@@ -8,7 +8,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import metrics, ops
 
 
 class L1Loss(nn.Module):
@@ -149,14 +149,69 @@ class PerceptualLoss(nn.Module):
         return loss, None
 
 
+class LPIPSLoss(nn.Module):
+    """loss_weight * mean over the batch of lpips.LPIPS(net='alex')(x, gt, normalize=True): the AlexNet LPIPS that
+    metrics.lpips reports, as a training term (include/cidnet_hip.h, "LPIPS training loss").  x, gt: fp32
+    (B,3,h,w) on the device in [0, 1] (nothing is clamped), h, w >= 31; gt is detached, as PerceptualLoss detaches it, and the
+    extractor is frozen, so the only gradient is d/dx.  forward returns a 0-dim fp32 tensor.
+    params: a metrics.LpipsParams, or the (alexnet path, heads path) pair metrics.load_lpips_params reads; nothing is shipped.
+    The parameters reach a device, and their data-gradient forms are made there, by prepare(device) -- which .to(device) /
+    .cuda() call, and which CIDNetLoss calls with the model's device when it is built -- or else on the first call on that
+    device.  Prepare before capturing a step: a captured step then holds no host-to-device copy and no host synchronisation.
+    The term computes in fp32 under set_precision("bf16") and set_storage_dtype too: its kernels have no other form."""
+
+    def __init__(self, params, loss_weight=1.0):
+        super().__init__()
+        self.params = metrics._lpips_params(params)
+        self.loss_weight = float(loss_weight)
+
+    def prepare(self, device):
+        """upload the frozen parameters to `device` and form their data-gradient copies there (once per device)"""
+        device = torch.device(device)
+        if device.type != "cuda":
+            return self
+        with torch.cuda.device(device):
+            self.params.on(device)
+            self.params.dgrad_on(device)
+        return self
+
+    def _apply(self, fn, *args, **kwargs):
+        # .to(device) / .cuda(): the module has no tensors of its own, so ask fn where it sends one
+        moved = fn(torch.empty(0))
+        if moved.is_cuda:
+            self.prepare(moved.device)
+        return super()._apply(fn, *args, **kwargs)
+
+    def forward(self, x, gt):
+        if x.dim() != 4 or x.shape[1] != 3 or gt.shape != x.shape:
+            raise RuntimeError("LPIPSLoss expects two (B,3,H,W) images of the same shape")
+        metrics.lpips_feature_sizes(*x.shape[-2:])              # ValueError under 31 x 31, before anything runs
+        ops._check(x, gt)
+        need = ops.needs_grad(x)
+        self.prepare(x.device)                                  # a dictionary hit after the first time
+        with torch.cuda.device(x.device):
+            return ops.LpipsLossFn.apply(x, gt.detach(), self.params, self.loss_weight, metrics.LPIPS_LAYERS, need)
+
+
 class CIDNetLoss(nn.Module):
     """loss_rgb + HVI_weight * loss_hvi with loss_* = L1 + SSIM + Edge + P_weight * Perceptual (train.py:61-65);
     defaults are data/options.py:56-59 (P_weight 1e-2 there; 0 here leaves the VGG term out, the round-1 objective).
     `model` supplies HVIT for the HVI-space terms, exactly as train.py calls `model.HVIT` on the output and on the ground
-    truth.  The perceptual term is built as train.py:192 does: conv1_2 / conv2_2 / conv3_4 / conv4_4, 'mse'."""
+    truth.  The perceptual term is built as train.py:192 does: conv1_2 / conv2_2 / conv3_4 / conv4_4, 'mse'.
+    lpips_weight > 0 (not in the reference; the default 0 builds nothing and leaves the objective as it is) adds
+    lpips_weight * LPIPSLoss(lpips_params)(output_rgb, gt_rgb) to loss_rgb only -- LPIPS of an HVI map means nothing;
+    lpips_params as LPIPSLoss takes them, and their absence is an error.  The term stays fp32 in the bf16 mode."""
 
-    def __init__(self, model, L1_weight=1.0, D_weight=0.5, E_weight=50.0, HVI_weight=1.0, P_weight=0.0, tnsm_weight=0.0):
+    def __init__(self, model, L1_weight=1.0, D_weight=0.5, E_weight=50.0, HVI_weight=1.0, P_weight=0.0, tnsm_weight=0.0,
+                 lpips_weight=0.0, lpips_params=None):
         super().__init__()
+        if lpips_weight > 0 and lpips_params is None:
+            raise ValueError(metrics._LPIPS_NO_PARAMS)
+        self.lpips = LPIPSLoss(lpips_params, loss_weight=lpips_weight) if lpips_weight > 0 else None
+        if self.lpips is not None:
+            p = next(iter(model.parameters()), None) if hasattr(model, "parameters") else None
+            if p is not None:
+                self.lpips.prepare(p.device)
         self.tnsm_weight = tnsm_weight
         self.l1 = L1Loss(loss_weight=L1_weight)
         self.ssim = SSIM(weight=D_weight)
@@ -191,6 +246,8 @@ class CIDNetLoss(nn.Module):
                              "or noise_map=...; a model in eval mode returns (rgb, None)")
         loss_hvi = self._terms(self._hvit(output_rgb), self._hvit(gt_rgb))
         loss_rgb = self._terms(output_rgb, gt_rgb)
+        if self.lpips is not None:
+            loss_rgb = loss_rgb + self.lpips(output_rgb, gt_rgb)
         loss = loss_rgb + self.hvi_weight * loss_hvi
         if self.tnsm_weight > 0:
             if im1 is None:

@@ -1202,11 +1202,13 @@ _LPIPS_NO_PARAMS = ("LPIPS needs torchvision's AlexNet weights and the lpips pac
 @dataclass(frozen=True)
 class LpipsParams:
     """The frozen parameters of lpips.LPIPS(net='alex'): per tap the convolution's weight (M,C,k,k) and bias (M), fp32 host
-    tensors in torchvision's shapes, and the 1x1 head as a (C_l,) fp32 tensor.  on(device) uploads them once per device."""
+    tensors in torchvision's shapes, and the 1x1 head as a (C_l,) fp32 tensor.  on(device) uploads them once per device;
+    dgrad_on(device) forms, once per device, the weights as the training loss's data gradients read them."""
     weights: tuple
     biases: tuple
     heads: tuple
     _dev: dict = field(default_factory=dict, repr=False, compare=False)      # device index -> (weights, biases, heads) there
+    _dgrad: dict = field(default_factory=dict, repr=False, compare=False)    # device index -> the five data-gradient weights
 
     def __post_init__(self):
         for name, got, want in _lpips_shapes(self.weights, self.biases, self.heads):
@@ -1219,6 +1221,20 @@ class LpipsParams:
             self._dev[key] = tuple(tuple(t.to(device, torch.float32).contiguous() for t in ts)
                                    for ts in (self.weights, self.biases, self.heads))
         return self._dev[key]
+
+    def dgrad_on(self, device):
+        """-> per layer the device weights in cidnet_lpips_dgrad_weights' form (flipped and transposed for the stride-1 layers,
+        phase-ordered for the first); the weights are frozen, so this happens once, outside any step"""
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        if key not in self._dgrad:
+            out = []
+            with torch.cuda.device(device):
+                for w, (_, m, c, k, stride, _, _) in zip(self.on(device)[0], LPIPS_LAYERS):
+                    wt = torch.empty(lib().raw("cidnet_lpips_dgrad_weights_floats")(m, c, k, stride), dtype=torch.float32, device=w.device)
+                    lib().call("cidnet_lpips_dgrad_weights", ops._p(w), ops._p(wt), m, c, k, stride, ops._stream())
+                    out.append(wt)
+            self._dgrad[key] = tuple(out)
+        return self._dgrad[key]
 
     @staticmethod
     def random(seed: int = 19) -> "LpipsParams":
@@ -1312,20 +1328,7 @@ def _lpips_extract(parts, prm):
         L.call("cidnet_metric_lpips_ingest", ops._p(q), ops._p(s), ops._p(x[i:]), q.shape[0], h, w, ops._stream())
         i += q.shape[0]
     weights, biases, _ = prm.on(dev)
-    feats, H, W = [], h, w
-    for l, (_, m, c, k, stride, pad, pooled) in enumerate(LPIPS_LAYERS):
-        if pooled:
-            Hp, Wp = (H - 3) // 2 + 1, (W - 3) // 2 + 1
-            y = torch.empty((N, c, Hp, Wp), dtype=torch.float32, device=dev)
-            L.call("cidnet_lpips_maxpool3s2", ops._p(x), ops._p(y), N * c, H, W, ops._stream())
-            x, H, W = y, Hp, Wp
-        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-        y = torch.empty((N, m, Ho, Wo), dtype=torch.float32, device=dev)
-        L.call("cidnet_lpips_conv_relu", ops._p(x), ops._p(weights[l]), ops._p(biases[l]), ops._p(y), N, m, c, H, W, k, stride,
-               pad, ops._stream())
-        feats.append(y)
-        x, H, W = y, Ho, Wo
-    return feats
+    return ops.lpips_taps(x, weights, biases, LPIPS_LAYERS)
 
 
 def _lpips_distance(f0, f1, prm, h, w, want_layers=True, want_score=True):

@@ -1465,6 +1465,105 @@ class PerceptualLossFn(torch.autograd.Function):
         return (_scaled(d, g, 1.0), None, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 7)
 
 
+def lpips_taps(x, weights, biases, layers):
+    """x: fp32 (N,3,h,w) behind the LPIPS ingest -> the five post-ReLU taps of AlexNet (include/cidnet_hip.h: LPIPS, step 2).
+    layers: metrics.LPIPS_LAYERS.  The caller has made the device current."""
+    N, _, H, W = x.shape
+    dev, L = x.device, lib()
+    feats = []
+    for l, (_, m, c, k, stride, pad, pooled) in enumerate(layers):
+        if pooled:
+            Hp, Wp = (H - 3) // 2 + 1, (W - 3) // 2 + 1
+            y = torch.empty((N, c, Hp, Wp), dtype=torch.float32, device=dev)
+            L.call("cidnet_lpips_maxpool3s2", _p(x), _p(y), N * c, H, W, _stream())
+            x, H, W = y, Hp, Wp
+        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+        y = torch.empty((N, m, Ho, Wo), dtype=torch.float32, device=dev)
+        L.call("cidnet_lpips_conv_relu", _p(x), _p(weights[l]), _p(biases[l]), _p(y), N, m, c, H, W, k, stride, pad, _stream())
+        feats.append(y)
+        x, H, W = y, Ho, Wo
+    return feats
+
+
+class LpipsLossFn(torch.autograd.Function):
+    """loss_weight * mean_b lpips.LPIPS(net='alex')(x_b, gt_b, normalize=True): include/cidnet_hip.h, "LPIPS training loss".
+    gt is a constant and the parameters are frozen, so the only gradient is d/dx.  params: a metrics.LpipsParams whose device
+    copies exist (on(), dgrad_on()), layers: metrics.LPIPS_LAYERS, need: whether a backward can follow (ops.needs_grad).
+    x and gt go through the extractor as one batch of 2 B.  Kept for the backward: the five taps of both halves, as the
+    extractor wrote them -- 4 (64 P0 + 192 P1 + 896 P2) bytes per image of either half, P_l the pixels of tap l: 5.1 MB for a
+    256 x 256 pair; the ground truth's half is read again by the distance derivative, which recomputes both norms.
+    No host synchronisation and no host-to-device copy: a captured step replays it."""
+
+    @staticmethod
+    def forward(ctx, x, gt, params, loss_weight, layers, need):
+        _check(x, gt)
+        x, gt = _c(x), _c(gt)
+        B, C, h, w = x.shape
+        if C != 3 or gt.shape != x.shape:
+            raise RuntimeError("LPIPSLoss expects two (B,3,H,W) images of the same shape")
+        dev, L = x.device, lib()
+        weights, biases, heads = params.on(dev)
+        z = torch.empty((2 * B, 3, h, w), dtype=torch.float32, device=dev)
+        L.call("cidnet_lpips_ingest_f32", _p(x), _p(z), B, h, w, _stream())
+        L.call("cidnet_lpips_ingest_f32", _p(gt), _p(z[B:]), B, h, w, _stream())
+        taps = lpips_taps(z, weights, biases, layers)
+        n = _raw("cidnet_lpips_loss_ws_floats", B, h, w)
+        ws = torch.empty(n, dtype=torch.float32, device=dev)
+        for l, t in enumerate(taps):
+            _, Cl, fh, fw = t.shape
+            L.call("cidnet_metric_lpips_layer", _p(t), _p(t[B:]), _p(heads[l]), _p(ws), n, l, B, Cl, fh, fw, h, w, _stream())
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        L.call("cidnet_lpips_loss_finish", _p(ws), n, _f(loss_weight), _p(loss), B, h, w, _stream())
+        ctx.taps = taps if need else None
+        ctx.meta = (params, float(loss_weight), layers, B, h, w)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        params, weight, layers, B, h, w = ctx.meta
+        taps = ctx.taps
+        if taps is None:
+            raise RuntimeError("LpipsLossFn: the taps kept for the backward were freed by the first backward pass (or never "
+                               "kept: need=False); a second pass through the same graph is not built")
+        dev, L = taps[0].device, lib()
+        heads = params.on(dev)[2]
+        wts = params.dgrad_on(dev)
+
+        def new(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+
+        def dist_grad(l, relu_mask):
+            t = taps[l]
+            _, Cl, fh, fw = t.shape
+            d = new(B, Cl, fh, fw)
+            L.call("cidnet_lpips_layer_bwd", _p(t), _p(t[B:]), _p(heads[l]), _p(d), _f(weight), relu_mask, B, Cl, fh * fw, _stream())
+            return d
+
+        d = dist_grad(4, 1)                      # the gradient at the output of the convolution of the layer being walked
+        for l in range(4, 0, -1):
+            _, m, c, k, stride, pad, pooled = layers[l]
+            fh, fw = taps[l].shape[-2:]          # stride 1: also the size of the convolution's input
+            below = taps[l - 1]
+            add = dist_grad(l - 1, 0)
+            dx = new(B, c, fh, fw)
+            if pooled:
+                L.call("cidnet_lpips_conv_dgrad", _p(d), _p(wts[l]), None, None, _p(dx), B, m, c, fh, fw, k, stride, pad, _stream())
+                Hs, Ws = below.shape[-2:]
+                d = new(B, c, Hs, Ws)
+                L.call("cidnet_lpips_maxpool3s2_bwd", _p(below), _p(dx), _p(add), _p(d), B * c, Hs, Ws, _stream())
+            else:
+                L.call("cidnet_lpips_conv_dgrad", _p(d), _p(wts[l]), _p(below), _p(add), _p(dx), B, m, c, fh, fw, k, stride, pad,
+                       _stream())
+                d = dx
+        _, m, c, k, stride, pad, _ = layers[0]
+        dz = new(B, 3, h, w)
+        L.call("cidnet_lpips_conv_dgrad", _p(d), _p(wts[0]), None, None, _p(dz), B, m, c, h, w, k, stride, pad, _stream())
+        gx = new(B, 3, h, w)
+        L.call("cidnet_lpips_ingest_f32_bwd", _p(dz), _p(gx), B, h, w, _stream())
+        ctx.taps = None
+        return _scaled(gx, g, 1.0), None, None, None, None, None
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
     _check(p, g, m, v)
     lib().call("cidnet_adam_step", _p(p), _p(g), _p(m), _p(v), p.numel(), _f(lr), _f(beta1), _f(beta2), _f(eps),

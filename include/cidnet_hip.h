@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 27
+#define CIDNET_ABI_VERSION 28
 
 int cidnet_abi_version(void);
 
@@ -911,7 +911,8 @@ int cidnet_ensemble_views(const float* x, float* y, int B, int C, int H, int W, 
 int cidnet_ensemble_merge(const float* ya, int na, const float* yb, int nb, float* out, int B, int C, int H, int W, void* stream);
 
 /* ---- LPIPS, AlexNet variant (lpips.LPIPS(net='alex'), version 0.1, lpips=True, spatial=False, eval mode: measure.py:78,
- * 145-153 of the reference), forward only (csrc/lpips.hip).  The definition, in the order the entries are used:
+ * 145-153 of the reference), the metric (csrc/lpips.hip; the training loss built on it follows below).  The definition, in the
+ * order the entries are used:
  *  (1) ingest:  x = u / 127.5 - 1 formed in fp64 and rounded once to fp32, then the scaling layer in fp32,
  *      (x - shift_c) / scale_c with shift = (-.030, -.088, -.188), scale = (.458, .448, .450).  u is the 8-bit value; with
  *      scale != NULL (GT mean) the fp64 value clip(u * scale[b], 0, 255), which is not re-quantized (measure.py:138-146).
@@ -953,6 +954,58 @@ long cidnet_metric_lpips_ws_floats(int B, int h, int w);
 int cidnet_metric_lpips_layer(const float* f0, const float* f1, const float* head, float* ws, long ws_floats, int layer, int B, int C,
                               int fh, int fw, int h, int w, void* stream);
 int cidnet_metric_lpips_finish(const float* ws, long ws_floats, double* layers, double* score, int B, int h, int w, void* stream);
+
+/* ---- LPIPS training loss (AlexNet; lpips.LPIPS(net='alex')(x, gt, normalize=True).mean() times a weight), forward through the
+ * entries above plus the three below, backward in csrc/lpips_loss.hip.  The contract:
+ * x, gt: fp32 (B,3,h,w), h, w >= 31, any value range (nothing clamps).  gt is a constant: the only gradient is d/dx.
+ *  (1) ingest (normalize=True): v = 2 x - 1 with one fp32 rounding (2 x is exact), then z = (v - shift_c) / scale_c in fp32, the
+ *      constants of the metric's step 1.  Backward: gx = (g / scale_c) * 2.  Compiled without contraction: both directions are
+ *      bit-identical to the same expression in fp32 torch.
+ *  (2) features: the five post-ReLU taps of the metric's step 2, through cidnet_lpips_conv_relu and cidnet_lpips_maxpool3s2.
+ *  (3) loss = weight * (1 / B) sum_b sum_l d_l(b), fp32, the d_l of the metric's step 3 from the same fixed-order fp64 partials.
+ *  (4) gradient rules.
+ *      ReLU: the gradient passes where the stored post-ReLU value is > 0.
+ *      Pool 3/2: a window's gradient goes to its first maximum in scan order, row-major inside the window (a later value
+ *        replaces the maximum only when strictly greater: ATen's rule, and cidnet_maxpool2_bwd's).  An input element sums the
+ *        windows that chose it (up to four) in window scan order; rows and columns under no window get 0.  Gather form, no
+ *        atomics.  A NaN never compares greater, so it is never chosen (torch would choose it).
+ *      Distance: with n = f / (s + 1e-10), s = sqrt(sum_c f_c^2), P_l the pixels of layer l and w_c its head,
+ *        dn_c = 2 w_c (n0_c - n1_c) weight / (B P_l),   df0_c = dn_c / (s + eps) - f0_c (sum_j dn_j f0_j) / (s (s + eps)^2).
+ *        A pixel whose f0 is all zero gets df0 = 0 in every channel.  torch's autograd gives NaN there (sqrt'(0) * 0) and the
+ *        formula's limit is dn / eps, about 1e10 times dn; but every channel of that pixel is 0, so the ReLU mask that follows
+ *        lets nothing through: zero is the value on which the kernel, the mask and the limit agree.  A ground-truth pixel with
+ *        s1 = 0 has n1 = 0, nothing special.  Per-pixel sums over channels in fp64 in a fixed order; the result is fp32.
+ *      Convolution data gradient: dx[b][c][iy][ix] = sum_{m,ky,kx} w[m][c][ky][kx] dy[b][m][oy][ox] with iy = S oy - PAD + ky;
+ *        fp32 products, fp32 accumulation, no dependence on the rest of the batch, no atomics, bit-identical from call to call.
+ * ingest_f32 / ingest_f32_bwd: step 1 and its backward, (B,3,h,w) -> (B,3,h,w).
+ * loss_finish: step 3 from the partials the five cidnet_metric_lpips_layer calls left in ws (cidnet_lpips_loss_ws_floats(B, h, w)
+ *   floats, 8-byte aligned; host-only query, 0 under 31 x 31): one wave, images in order, layers in order, fp64, one rounding.
+ * dgrad_weights: the frozen weights w (M,C,ksize,ksize) in the form a data gradient reads, written once per device.
+ *   stride 1: wt (C,M,ksize,ksize), spatially flipped (the gradient as a convolution of dy).  stride 4 (ksize 11, C 3 only):
+ *   wt (11,11,M,4) = the three channels of a (ky, kx, m) and a zero, read 16 bytes at a time: this wt must be 16-byte aligned
+ *   (conv_dgrad returns CIDNET_ERR_ARG otherwise).  dgrad_weights_floats: its length; 0 = not taken.
+ * conv_dgrad: dx (B,C,H,W) from dy (B,M,Ho,Wo) and wt = dgrad_weights of the layer (M,C,ksize,ksize), (ksize, stride, pad) one
+ *   of (11, 4, 2) with C = 3, (5, 1, 2), (3, 1, 1) with C a multiple of 64; else CIDNET_ERR_SHAPE.  tap, addend: both NULL,
+ *   or both (B,C,H,W) (stride 1 only): dx = tap > 0 ? dx + addend : 0 -- the ReLU mask of the tap dx is the gradient of and
+ *   that tap's distance gradient.  Stride 1 runs the implicit GEMM of conv_relu on the fp32 matrix cores; stride 4 is a
+ *   gather of the at most 3 x 3 windows that reach a pixel: pixels under no window get exactly 0.
+ * maxpool3s2_bwd: gx (planes,H,W) from x (planes,H,W) and gy (planes,Ho,Wo) by the pool rule above; addend (planes,H,W) or
+ *   NULL: with it, x is a post-ReLU tap and gx = x > 0 ? gx + addend : 0.  H < 3 or W < 3 is CIDNET_ERR_SHAPE.
+ * layer_bwd: g (B,C,P) = df0 of the distance rule above for f0, f1 (B,C,P), head C floats, with `weight` the loss weight
+ *   (the kernel divides by B P in fp64); relu_mask != 0 also zeroes g where f0 <= 0 (the deepest tap has no other mask).
+ *   lpips_dist_kernel's layout: eight threads a pixel, meeting in LDS in group order. */
+int cidnet_lpips_ingest_f32(const float* x, float* z, int B, int h, int w, void* stream);
+int cidnet_lpips_ingest_f32_bwd(const float* g, float* gx, int B, int h, int w, void* stream);
+long cidnet_lpips_loss_ws_floats(int B, int h, int w);
+int cidnet_lpips_loss_finish(const float* ws, long ws_floats, float weight, float* loss, int B, int h, int w, void* stream);
+long cidnet_lpips_dgrad_weights_floats(int M, int C, int ksize, int stride);
+int cidnet_lpips_dgrad_weights(const float* w, float* wt, int M, int C, int ksize, int stride, void* stream);
+int cidnet_lpips_conv_dgrad(const float* dy, const float* wt, const float* tap, const float* addend, float* dx, int B, int M, int C,
+                            int H, int W, int ksize, int stride, int pad, void* stream);
+int cidnet_lpips_maxpool3s2_bwd(const float* x, const float* gy, const float* addend, float* gx, long planes, int H, int W,
+                                void* stream);
+int cidnet_lpips_layer_bwd(const float* f0, const float* f1, const float* head, float* g, float weight, int relu_mask, int B, int C,
+                           long P, void* stream);
 
 /* ---- CIEDE2000 colour difference (csrc/ciede2000.hip): the mean dE00 between the restored image (colour 1) and its ground
  * truth (colour 2), the colour-fidelity number of the low-light literature, usually computed with scikit-image as
