@@ -193,6 +193,29 @@ class LPIPSLoss(nn.Module):
             return ops.LpipsLossFn.apply(x, gt.detach(), self.params, self.loss_weight, metrics.LPIPS_LAYERS, need)
 
 
+class FFTLoss(nn.Module):
+    """loss_weight * F.l1_loss(view_as_real(rfft2(pred, norm=norm)), view_as_real(rfft2(target, norm=norm))): the L1 distance of
+    the half spectra that MIMO-UNet / DeepRFT add to a restoration objective (include/cidnet_hip.h, "frequency-domain training
+    loss").  pred, target: fp32 (B,C,H,W) on the device, any H, W from 1 to 2048; differentiable in both.
+    norm: "backward" (unnormalised, torch's default) or "ortho".  forward returns a 0-dim fp32 tensor.  The term computes in
+    fp32 under set_precision("bf16") and set_storage_dtype too: its kernels have no other form."""
+
+    def __init__(self, loss_weight=1.0, norm="backward"):
+        super().__init__()
+        if norm not in ops.FFT_NORMS:
+            raise ValueError(f"FFTLoss: norm must be 'backward' or 'ortho' (got {norm!r})")
+        if not (0.0 <= float(loss_weight) < float("inf")):
+            raise ValueError(f"FFTLoss: loss_weight must be finite and not negative (got {loss_weight!r})")
+        self.loss_weight = float(loss_weight)
+        self.norm = norm
+
+    def forward(self, pred, target):
+        if pred.dim() != 4 or target.shape != pred.shape:
+            raise RuntimeError("FFTLoss expects two (B,C,H,W) tensors of the same shape")
+        ops._check(pred, target)
+        return ops.FFTLossFn.apply(pred, target, self.loss_weight, self.norm)
+
+
 class CIDNetLoss(nn.Module):
     """loss_rgb + HVI_weight * loss_hvi with loss_* = L1 + SSIM + Edge + P_weight * Perceptual (train.py:61-65);
     defaults are data/options.py:56-59 (P_weight 1e-2 there; 0 here leaves the VGG term out, the round-1 objective).
@@ -200,11 +223,16 @@ class CIDNetLoss(nn.Module):
     truth.  The perceptual term is built as train.py:192 does: conv1_2 / conv2_2 / conv3_4 / conv4_4, 'mse'.
     lpips_weight > 0 (not in the reference; the default 0 builds nothing and leaves the objective as it is) adds
     lpips_weight * LPIPSLoss(lpips_params)(output_rgb, gt_rgb) to loss_rgb only -- LPIPS of an HVI map means nothing;
-    lpips_params as LPIPSLoss takes them, and their absence is an error.  The term stays fp32 in the bf16 mode."""
+    lpips_params as LPIPSLoss takes them, and their absence is an error.  The term stays fp32 in the bf16 mode.
+    fft_weight > 0 (not in the reference either; the default 0 builds nothing) adds FFTLoss(fft_weight, fft_norm) to loss_*:
+    a signal-level term like L1 / SSIM / Edge, so it counts in RGB and, scaled by HVI_weight, in HVI space."""
 
     def __init__(self, model, L1_weight=1.0, D_weight=0.5, E_weight=50.0, HVI_weight=1.0, P_weight=0.0, tnsm_weight=0.0,
-                 lpips_weight=0.0, lpips_params=None):
+                 lpips_weight=0.0, lpips_params=None, fft_weight=0.0, fft_norm="backward"):
         super().__init__()
+        if fft_weight < 0:
+            raise ValueError(f"CIDNetLoss: fft_weight must not be negative (got {fft_weight!r})")
+        self.fft = FFTLoss(loss_weight=fft_weight, norm=fft_norm) if fft_weight > 0 else None
         if lpips_weight > 0 and lpips_params is None:
             raise ValueError(metrics._LPIPS_NO_PARAMS)
         self.lpips = LPIPSLoss(lpips_params, loss_weight=lpips_weight) if lpips_weight > 0 else None
@@ -226,6 +254,8 @@ class CIDNetLoss(nn.Module):
         t = self.l1(a, b) + self.ssim(a, b) + self.edge(a, b)
         if self.perceptual is not None:
             t = t + self.p_weight * self.perceptual(a, b)[0]
+        if self.fft is not None:
+            t = t + self.fft(a, b)
         return t
 
     # dp.DataParallelTrainer passes the step's input as `im1=` to a loss function with this attribute

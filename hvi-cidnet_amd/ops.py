@@ -1564,6 +1564,142 @@ class LpipsLossFn(torch.autograd.Function):
         return _scaled(gx, g, 1.0), None, None, None, None, None
 
 
+# --------------------------------------------------------------------------------------------
+# frequency-domain training loss (include/cidnet_hip.h, "frequency-domain training loss"; csrc/fft_loss.hip)
+# --------------------------------------------------------------------------------------------
+FFT_NORMS = {"backward": 0, "ortho": 1}
+# (device, N, Nk) -> the (N, Nk, 2) twiddle table.  Never evicted: a captured step bakes the addresses in, and a table freed
+# and rebuilt elsewhere would leave the replay reading freed memory.  A shape costs 8 N Nk bytes (H = W = 2048: 25 MB).
+_DFT_TABLES = {}
+
+
+def dft_table(N, Nk, device):
+    """the cached (N, Nk, 2) fp32 table of (cos, -sin)(2 pi n k / N) on `device`, built on first use (not during a capture:
+    _dft_tables places the tables in the call's workspace then)"""
+    device = torch.device(device)
+    key = (device.type, device.index, int(N), int(Nk))
+    t = _DFT_TABLES.get(key)
+    if t is None:
+        with torch.cuda.device(device):
+            t = torch.empty((int(N), int(Nk), 2), device=device, dtype=torch.float32)
+            lib().call("cidnet_dft_table", int(N), int(Nk), _p(t), _stream())
+            # the creating stream may not be the one of later users: make the table globally visible once
+            torch.cuda.current_stream().synchronize()
+        _DFT_TABLES[key] = t
+    return t
+
+
+def _dft_tables(device, H, W):
+    """-> (tab_h, tab_w, owner) for one call of the term on the current stream: the cached tables (owner None), or, on the
+    first use of a shape inside a capture (nothing can be synchronised there), tables written into a buffer of the call's own
+    (owner: hold it until the call is enqueued), as bilinear_bwd does"""
+    Wh = W // 2 + 1
+    keys = [(device.type, device.index, H, H), (device.type, device.index, W, Wh)]
+    if all(k in _DFT_TABLES for k in keys) or not torch.cuda.is_current_stream_capturing():
+        return dft_table(H, H, device), dft_table(W, Wh, device), None
+    extra = torch.empty(2 * H * H + 2 * W * Wh, device=device, dtype=torch.float32)
+    th, tw = extra[:2 * H * H], extra[2 * H * H:]
+    lib().call("cidnet_dft_table", H, H, _p(th), _stream())
+    lib().call("cidnet_dft_table", W, Wh, _p(tw), _stream())
+    return th, tw, extra
+
+
+def _fft_ws(P, H, W, device):
+    n = int(_raw("cidnet_fft_loss_ws_floats", P, H, W))
+    if n == 0:
+        raise RuntimeError(f"the frequency-domain loss does not take {P} planes of {H} x {W} (sides 1..2048, 2 P H (W/2+1) < 2^31)")
+    return _ws(n, device), n
+
+
+def _planes(x):
+    if x.dim() < 2:
+        raise RuntimeError("expected (..., H, W)")
+    H, W = x.shape[-2:]
+    P = x.numel() // max(H * W, 1)
+    return P, H, W
+
+
+def rfft2_parts(x):
+    """x fp32 (..., H, W) on the device -> (..., H, W // 2 + 1, 2): (Re, Im) of torch.fft.rfft2(x), on the fp32 matrix cores"""
+    _check(x)
+    x = _c(x)
+    P, H, W = _planes(x)
+    with torch.cuda.device(x.device):
+        ws, n = _fft_ws(P, H, W, x.device)                        # refuses the shape before anything is built
+        th, tw, _keep = _dft_tables(x.device, H, W)
+        D = torch.empty(x.shape[:-1] + (W // 2 + 1, 2), device=x.device, dtype=torch.float32)
+        lib().call("cidnet_rfft2_fwd", _p(x), _p(th), _p(tw), _p(D), _p(ws), n, P, H, W, _stream())
+    return D
+
+
+def rfft2_parts_adjoint(S, W):
+    """S fp32 (..., H, W // 2 + 1, 2) -> (..., H, W): the adjoint of rfft2_parts (the vjp of rfft2 with cotangent S_r + i S_i)"""
+    _check(S)
+    S = _c(S)
+    W = int(W)
+    if S.dim() < 3 or S.shape[-1] != 2 or S.shape[-2] != W // 2 + 1:
+        raise RuntimeError("rfft2_parts_adjoint expects (..., H, W // 2 + 1, 2)")
+    H = S.shape[-3]
+    P = S.numel() // (H * S.shape[-2] * 2)
+    with torch.cuda.device(S.device):
+        ws, n = _fft_ws(P, H, W, S.device)
+        th, tw, _keep = _dft_tables(S.device, H, W)
+        g = torch.empty(S.shape[:-3] + (H, W), device=S.device, dtype=torch.float32)
+        lib().call("cidnet_rfft2_adj", _p(S), _p(th), _p(tw), _p(g), _p(ws), n, P, H, W, _stream())
+    return g
+
+
+class FFTLossFn(torch.autograd.Function):
+    """weight * l1_loss(view_as_real(rfft2(a, norm)), view_as_real(rfft2(b, norm))) for fp32 (B,C,H,W) a, b, differentiable in
+    both: include/cidnet_hip.h, "frequency-domain training loss".  norm: "backward" or "ortho".  Kept for the backward: the
+    signs of the spectrum's parts, S (B,C,H,W//2+1,2) fp32 -- a tensor of its own, not the stream's scratch buffer, which the
+    launches in between overwrite.  fp32 in every precision mode.  No host synchronisation and no host-to-device copy (the
+    twiddle tables of a shape are built once, ops.dft_table): a captured step replays it."""
+
+    @staticmethod
+    def forward(ctx, a, b, weight, norm):
+        if norm not in FFT_NORMS:
+            raise ValueError(f"FFTLoss: norm must be 'backward' or 'ortho' (got {norm!r})")
+        _check(a, b)
+        if a.dim() != 4 or a.shape != b.shape:
+            raise RuntimeError("FFTLoss expects two (B,C,H,W) tensors of the same shape")
+        a, b = _c(a), _c(b)
+        B, C, H, W = a.shape
+        P = B * C
+        need = any(ctx.needs_input_grad[:2])
+        dev = a.device
+        with torch.cuda.device(dev):
+            ws, n = _fft_ws(P, H, W, dev)
+            th, tw, _keep = _dft_tables(dev, H, W)
+            S = torch.empty((B, C, H, W // 2 + 1, 2), device=dev, dtype=torch.float32) if need else None
+            loss = torch.empty((), device=dev, dtype=torch.float32)
+            lib().call("cidnet_fft_loss_fwd", _p(a), _p(b), _p(th), _p(tw), _f(weight), FFT_NORMS[norm], _p(loss), _p(S), _p(ws), n,
+                       P, H, W, _stream())
+        ctx.S = S
+        ctx.meta = (float(weight), FFT_NORMS[norm], B, C, H, W)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        weight, norm, B, C, H, W = ctx.meta
+        S = ctx.S
+        if S is None:
+            raise RuntimeError("FFTLossFn: the signs kept for the backward were freed by the first backward pass (or never kept: "
+                               "no input required a gradient); a second pass through the same graph is not built")
+        need_a, need_b = ctx.needs_input_grad[:2]
+        dev = S.device
+        g = g.to(torch.float32).reshape(1).contiguous()
+        with torch.cuda.device(dev):
+            ws, n = _fft_ws(B * C, H, W, dev)
+            th, tw, _keep = _dft_tables(dev, H, W)
+            ga = torch.empty((B, C, H, W), device=dev, dtype=torch.float32) if need_a else None
+            gb = torch.empty((B, C, H, W), device=dev, dtype=torch.float32) if need_b else None
+            lib().call("cidnet_fft_loss_bwd", _p(S), _p(th), _p(tw), _p(g), _f(weight), norm, _p(ga), _p(gb), _p(ws), n, B * C, H, W,
+                       _stream())
+        ctx.S = None
+        return ga, gb, None, None
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
     _check(p, g, m, v)
     lib().call("cidnet_adam_step", _p(p), _p(g), _p(m), _p(v), p.numel(), _f(lr), _f(beta1), _f(beta2), _f(eps),

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CIDNET_ABI_VERSION 28
+#define CIDNET_ABI_VERSION 29
 
 int cidnet_abi_version(void);
 
@@ -1102,6 +1102,48 @@ int cidnet_metric_brisque_fit(const double* moments, int tiles, double* feat, in
 int cidnet_metric_brisque_svr(const double* feat, const double* sv, const double* coef, const double* fmin, const double* fmax,
                               const double* rho_gamma, int n_sv, double* score, int B, void* stream);
 int cidnet_metric_brisque_features(const uint8_t* rgb, double* feat, float* ws, long ws_floats, int B, int h, int w, void* stream);
+
+/* ---- frequency-domain training loss (csrc/fft_loss.hip): an L1 distance between the half spectra of the
+ * prediction a and the target b, fp32 (P,H,W) planes (P = B C), the term MIMO-UNet / DeepRFT add to a restoration objective.
+ * The reference has none; the contract is this text, and torch.fft.rfft2 in fp64 is the oracle.  With d = a - b, Wh = W / 2 + 1:
+ *   D[p,ky,kx] = sum_y sum_x d[p,y,x] exp(-2 pi i (ky y / H + kx x / W)),   ky < H, kx < Wh
+ *   loss = weight s / (2 P H Wh) sum (|Re D| + |Im D|),   s = 1 (norm 0, "backward") or 1 / sqrt(H W) (norm 1, "ortho")
+ *        = weight * l1_loss(view_as_real(rfft2(a, norm)), view_as_real(rfft2(b, norm)))
+ *   dloss/da[p,y,x] = gloss weight s / (2 P H Wh) sum_{ky,kx} (sign(Re D) cos t - sign(Im D) sin t),  sign(0) = 0;  dloss/db = -dloss/da
+ * -- the plain adjoint of the half spectrum, no Hermitian doubling: what autograd gives.
+ * Each axis is a GEMM against a twiddle table on the fp32 matrix cores (fp32 products, fp32 accumulation over k in ascending
+ * order), so every H x W up to 2048 a side is taken.  fp32 in every precision mode.  No atomics: bit-identical from call to
+ * call; a plane's spectrum, signs and gradient do not depend on the other planes.
+ * dft_table: table (N, Nk, 2) = (cos, -sin)(2 pi m / N), m = n k mod N reduced in integers, evaluated in fp64 and rounded once;
+ *   exactly 0 / +-1 where 4 m is a multiple of N, so a purely real bin gets an imaginary part of exactly 0 and sign 0.
+ *   N or Nk < 1 or a NULL / misaligned table is CIDNET_ERR_ARG; N > 2048 or Nk > N is CIDNET_ERR_SHAPE.
+ * tab_h = dft_table(H, H), tab_w = dft_table(W, Wh) in all that follows; they are only read.
+ * ws: cidnet_fft_loss_ws_floats(P, H, W) floats, 8-byte aligned, for every entry (host-only query; 0 for a refused shape).
+ * loss_fwd: loss (1 float).  S NULL: nothing else is written -- the spectrum never goes to memory.  S (P,H,Wh,2): the signs of
+ *   (Re D, Im D) as fp32 +-1 / 0, what loss_bwd reads.  a - b is formed while staging.  The sum of |.| is fp32 over the 16 values
+ *   a lane holds, fp64 from there on: one fp64 partial per block in a fixed slot, one block adds the slots in a fixed order.
+ *   Identical a and b give exactly 0.
+ * loss_bwd: ga and / or gb = -ga (P,H,W), bit for bit each other's negation; either may be NULL (both: nothing is launched).
+ *   gloss: the upstream gradient, one float on the device.  weight and norm as given to loss_fwd.
+ * rfft2_fwd: D (P,H,Wh,2) = (Re, Im) of the unnormalised half spectrum of x.  rfft2_adj: g (P,H,W) = the adjoint of that map
+ *   applied to Sin (P,H,Wh,2), g[y,x] = sum Sin_r cos t - Sin_i sin t.  The two linear maps on their own, for the tests.
+ * plan: host only, launches nothing; the function the launchers' sizes come from.  Writes out[0..16] = the tile MT, NT, KC; the
+ *   grids (x, y, z) of the row forward, the column forward, the column adjoint and the row adjoint; the number of fp64
+ *   partials; the workspace floats.  out NULL or n < 17 is CIDNET_ERR_ARG; never writes past out[16].
+ * Errors, before any launch and with nothing written: P, H or W < 1, a NULL (but S, ga, gb) or misaligned pointer (4 bytes; ws
+ *   8), norm outside {0, 1}, a negative, NaN or infinite weight: CIDNET_ERR_ARG.  H or W > 2048, P > 65535, P H W or
+ *   2 P H Wh > 2^31 - 1: CIDNET_ERR_SHAPE.  A short workspace: CIDNET_ERR_WS. */
+int cidnet_dft_table(int N, int Nk, float* table, void* stream);
+long cidnet_fft_loss_ws_floats(int P, int H, int W);
+int cidnet_fft_loss_plan(int P, int H, int W, long* out, int n);
+int cidnet_fft_loss_fwd(const float* a, const float* b, const float* tab_h, const float* tab_w, float weight, int norm, float* loss,
+                        float* S, float* ws, long ws_floats, int P, int H, int W, void* stream);
+int cidnet_fft_loss_bwd(const float* S, const float* tab_h, const float* tab_w, const float* gloss, float weight, int norm, float* ga,
+                        float* gb, float* ws, long ws_floats, int P, int H, int W, void* stream);
+int cidnet_rfft2_fwd(const float* x, const float* tab_h, const float* tab_w, float* D, float* ws, long ws_floats, int P, int H, int W,
+                     void* stream);
+int cidnet_rfft2_adj(const float* Sin, const float* tab_h, const float* tab_w, float* g, float* ws, long ws_floats, int P, int H, int W,
+                     void* stream);
 
 #ifdef __cplusplus
 }
